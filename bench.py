@@ -1,6 +1,11 @@
 """bench.py -- the BASELINE.json metric on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times K steps and prints the headline line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, ...) and nothing else.  `--dump-outputs DIR` writes what the last timed step
+returned as float32 .npy files (see dump_outputs).  `--full` adds everything beyond the headline: the objects listed below,
+the parity check against the reference's own run and the host-enqueue diagnostic (`--no-*` switch single legs off).
 
 N > 1: one process per GPU over RCCL (torch.distributed backend "nccl").  Started as the driver starts it
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...`) the ranks read
@@ -24,7 +29,7 @@ layer (univs_amd/distributed.py) -- measured right after the replica loop in the
 Nothing is measured inside the timed region except the steps themselves: per-kernel times for the roofline objects
 come from a separate instrumented pass after it (HIP events on the launch stream around each operator call).
 
-Extra objects on the JSON line (tier contract): `roofline` (MSDeformAttn forward, algorithmic bytes 3200*S per frame
+Extra objects on the JSON line with `--full` (tier contract): `roofline` (MSDeformAttn forward, algorithmic bytes 3200*S per frame
 per launch), `roofline_mask_decode` (the full-resolution launch) and `roofline_mask_decode_family`
 (the ten prediction-head calls of a clip under the un-fused op-boundary accounting of SURVEY.md section 8d: 4.197 GB per
 clip over the summed time of every kernel the fused implementation runs for them), `roofline_window_attn` (per Swin
@@ -62,6 +67,11 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float32; rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline (other configs, sliding loop, rooflines, "
+                         "parity against golden g12, cpu_baseline)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the cpu_baseline leg (default: min(cores, 32))")
     ap.add_argument("--no-frame-sharded", action="store_true", help="skip the config-3 frame-sharded measurement (N>1: one clip "
@@ -137,6 +147,31 @@ def timed_loop(step, steps, warmup, world, sync, dev):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     return dt, out
+
+
+DUMP_MAX_ELEMENTS = 1 << 23        # per array: 32 MB of float32; the config-2 line writes 35.6 MB in all
+DUMP_SEED = 0
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: every floating-point tensor of the step's output dict as `path/<key>.npy` (float32).  An array of more
+    than DUMP_MAX_ELEMENTS elements (pred_masks: [1, 100, 5, 184, 320] = 118 MB at config 2) is written as `<key>_sample.npy`:
+    the elements at DUMP_MAX_ELEMENTS flat indices drawn without replacement by numpy.random.default_rng(DUMP_SEED), ascending --
+    the same indices in every run of the same shape."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for k, v in out.items():
+        if not isinstance(v, torch.Tensor) or not v.is_floating_point():
+            continue
+        v, name = v.detach(), k
+        if v.numel() > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(v.numel(), DUMP_MAX_ELEMENTS, replace=False))
+            v, name = v.reshape(-1)[torch.from_numpy(idx).to(v.device)], k + "_sample"
+        a = v.float().cpu().numpy()
+        total += a.nbytes
+        assert total <= 64 << 20, f"--dump-outputs: {total} bytes is over the 64 MB budget"
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 class OpTimer:
@@ -331,16 +366,8 @@ def run(args):
 
     sync = torch.cuda.synchronize
     dt, out = timed_loop(step, args.steps, args.warmup, world, sync, dev)
-    # diagnostic, outside the timed region: how long the host needs to ENQUEUE a clip (python + launch overhead + any
-    # host-device synchronisation inside the model).  Close to ms_per_step = the clip is host-bound, not GPU-bound.
-    sync()
-    t_enq = []
-    for _ in range(3):
-        t0 = time.perf_counter()
-        step()
-        t_enq.append(time.perf_counter() - t0)
-        sync()
-    host_enqueue_ms = sorted(t_enq)[1] * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
 
     res = {
         "metric": "frames/sec per node, 720p T=5 clip, Swin-T 100Q; mask-logit max-abs-err",
@@ -350,7 +377,6 @@ def run(args):
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": dt / args.steps * 1e3,
-        "host_enqueue_ms_per_step": host_enqueue_ms,
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -369,8 +395,20 @@ def run(args):
         res["rccl"] = {"ranks": dist.get_world_size(), "backend": dist.get_backend(),
                        "version": ".".join(str(v) for v in torch.cuda.nccl.version())}
 
+    if args.full:
+        # diagnostic, outside the timed region: how long the host needs to ENQUEUE a clip (python + launch overhead + any
+        # host-device synchronisation inside the model).  Close to ms_per_step = the clip is host-bound, not GPU-bound.
+        sync()
+        t_enq = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            step()
+            t_enq.append(time.perf_counter() - t0)
+            sync()
+        res["host_enqueue_ms_per_step"] = sorted(t_enq)[1] * 1e3
+
     # ---- BASELINE config 3: one clip of 5*N frames sharded by frame over the N ranks (T=40 at N=8)
-    if world > 1 and not args.no_frame_sharded:
+    if args.full and world > 1 and not args.no_frame_sharded:
         from univs_amd.distributed import FrameShard
         head.predictor.frame_shard = FrameShard()
         fr_s = synth.synthetic_frames(T, case["H"], case["W"], f"frames/rank{rank}").to(dev)
@@ -397,7 +435,7 @@ def run(args):
     # ---- N = 1 anchor of the frame-sharded path: ONE 40-frame 720p clip (config 3's single-clip reading: position_encoding.py:123
     # allows 128 frames) through FrameShard under a ONE-rank RCCL group, collectives issued for real -- the denominator a
     # later 8-GPU number of `frame_sharded` needs, and the sharded code path on hardware at all
-    if world == 1 and not args.no_frame_sharded:
+    if args.full and world == 1 and not args.no_frame_sharded:
         try:
             import socket
             from univs_amd.distributed import FrameShard
@@ -492,7 +530,7 @@ def run(args):
 
     # ---- BASELINE config 5 (Swin-L, T=10 @ 1080p, 200 queries, "MFMA window-attn, fp16"): one clip with the window-attention
     # products on fp16 operands (the variant the config names) and one with the exact-f32 products, on rank 0 at N = 1
-    if world == 1 and not args.no_config5:
+    if args.full and world == 1 and not args.no_config5:
         try:
             c5 = cases.CFG5
             swin5 = helpers.build_swin(dev, variant=cases.SWIN_L)
@@ -542,7 +580,7 @@ def run(args):
     #          pixel decoder once per FRAME (inference/video_entity.py: pixel_decoder_once_per_window);
     #   N > 1: the frames of the video spread over the N ranks (frame f on rank f % N: InferenceVideoEntity.set_frame_shard), every
     #          clip's decoder on the ranks that own its frames with one all-gather of the query states per layer, per-video state replicated.
-    if not args.no_sliding_loop:
+    if args.full and not args.no_sliding_loop:
         try:
             import types
             from univs_amd.inference.video_entity import InferenceVideoEntity, normalized_image_list
@@ -651,7 +689,7 @@ def run(args):
     # ---- BASELINE config 4: Swin-B (12 x 12 windows), T=5 @ 720p, 200 learnable queries + 4 referring expressions: the text-prompt
     # path (78 text tokens per expression cross-attend to the three feature levels, ...decoder_univs.py:760-793; ProCA; 'sep-blocked'
     # self-attention).  Parity at this size: tests/test_modules_gpu.py (golden g14 / g14b); here its cost, on rank 0 at N = 1
-    if world == 1 and not args.no_config4:
+    if args.full and world == 1 and not args.no_config4:
         try:
             c4 = cases.CFG4
             swin4 = helpers.build_swin(dev, variant=cases.SWIN_B)
@@ -690,6 +728,11 @@ def run(args):
             dist.barrier()
             dist.destroy_process_group()
         return None
+    if not args.full:
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return json.dumps(res)
 
     # ---- parity of the timed path against the reference's own CPU run (tests/golden/g12)
     try:
@@ -960,7 +1003,10 @@ def run(args):
         # each; a count whose warm-up is already 2x slower than the best so far is dropped) and reports the BEST count, with two
         # more timed clips there (median of three); --cpu-threads N pins the count.
         ncpu = os.cpu_count() or 1
-        cands = [args.cpu_threads] if args.cpu_threads > 0 else sorted({min(ncpu, c) for c in (32, 64, 128)})
+        # never more threads than the process may use: its affinity mask, and OMP_NUM_THREADS where the caller set it
+        omp = os.environ.get("OMP_NUM_THREADS", "").split(",")[0]
+        usable = min(len(os.sched_getaffinity(0)), int(omp) if omp.isdigit() and int(omp) > 0 else ncpu)
+        cands = [args.cpu_threads] if args.cpu_threads > 0 else sorted({min(usable, c) for c in (32, 64, 128)})
         sweep, timed = {}, {}
         for c_ in cands:
             torch.set_num_threads(c_)

@@ -1184,6 +1184,83 @@ def g21_result_files():
     save("g21_result_files", **out)
 
 
+@gen
+def g22_long_video_split():
+    """univs_prompt_longvideo.py:562-571 on the reference's head: what the attributes the long-video model reads (pe_layer,
+    input_proj[i], level_embed) give on its own maps.  The maps (forward_features) are g3's, the split call's outputs g6's
+    (bit-identical: the reference's head runs forward_features -> predictor); an input_proj output is stored only where it
+    is not the map itself (an empty Sequential when in_channels == hidden_dim)."""
+    R = rh.ref()
+    case = cases.HEAD_CASE
+    head = _ref_head(R, case)
+    _, _, _, ms = head.pixel_decoder.forward_features(cases.backbone_features(case))
+    p = head.predictor
+    arrays = dict(n_ms=len(ms), level_embed=p.level_embed.weight, num_classes=head.num_classes)
+    for i in range(3):
+        y = p.input_proj[i](ms[i])
+        if not torch.equal(y, ms[i]):
+            arrays[f"input_proj{i}"] = y
+    x = ms[0]
+    arrays["pe_ms0"] = p.pe_layer(x.view(1, case["T"], -1, *x.shape[-2:]), None)
+    save("g22_long_video_split", **arrays)
+
+BPE_PLACEHOLDER = "\u4e01 \u4e01"     # a pair of a character no byte-level pre-token contains: never merged
+
+
+@gen
+def bpe_merges_subset():
+    """tests/golden/bpe_merges_subset.txt.gz: OpenAI CLIP's public merge table (bpe_simple_vocab_16e6.txt.gz, MIT licence;
+    UNIVS_BPE_VOCAB or the reference's copy) cut down to what the tests tokenize.  Every merge the BPE applies to a pre-token
+    that reaches SimpleTokenizer.bpe while the tokenizer tests run keeps its rank; every other rank holds BPE_PLACEHOLDER.
+    Token ids (ranks, <|startoftext|> / <|endoftext|> after the last rank) and the merges chosen are those of the full table:
+    a merge that is never the lowest-ranked pair of a pre-token never decides anything."""
+    import gzip
+    import pytest
+    from univs_amd.modeling.language import tokenizer as tk
+    full = os.environ.get("UNIVS_BPE_VOCAB") or os.path.join(rh.REF_ROOT, "univs", "modeling", "language",
+                                                             "bpe_simple_vocab_16e6.txt.gz")
+    words, orig = set(), tk.SimpleTokenizer.bpe
+
+    def recording(self, token):
+        words.add(token)
+        return orig(self, token)
+    tk.SimpleTokenizer.bpe = recording
+    os.environ["UNIVS_BPE_VOCAB"] = full
+    try:
+        rc = pytest.main(["-q", "-p", "no:cacheprovider", os.path.join(ROOT, "tests", "test_language_cpu.py"),
+                          os.path.join(ROOT, "tests", "test_prepare_targets_cpu.py"),
+                          os.path.join(ROOT, "tests", "test_meta_arch_cpu.py") + "::test_custom_text_request_goes_from_raw_text_to_masks"])
+    finally:
+        tk.SimpleTokenizer.bpe = orig
+    assert rc == 0, rc
+    tok = tk.SimpleTokenizer(full)
+    used = set()
+    for w in words - {tk._SOT, tk._EOT}:
+        parts = list(w[:-1]) + [w[-1] + tk._WORD_END]
+        while len(parts) > 1:
+            ranked = [(tok.bpe_ranks[p], p) for p in zip(parts[:-1], parts[1:]) if p in tok.bpe_ranks]
+            if not ranked:
+                break
+            r, best = min(ranked)
+            used.add(r)
+            fused, i = [], 0
+            while i < len(parts):
+                if i + 1 < len(parts) and (parts[i], parts[i + 1]) == best:
+                    fused.append(parts[i] + parts[i + 1])
+                    i += 2
+                else:
+                    fused.append(parts[i])
+                    i += 1
+            parts = fused
+    with gzip.open(full) as f:
+        lines = f.read().decode("utf-8").split("\n")
+    out = [lines[0]] + [lines[1 + r] if r in used else BPE_PLACEHOLDER for r in range(tk._N_MERGES)]
+    path = os.path.join(OUT, "bpe_merges_subset.txt.gz")
+    with open(path, "wb") as raw, gzip.GzipFile(fileobj=raw, mode="wb", mtime=0) as f:
+        f.write("\n".join(out).encode("utf-8"))
+    print(f"wrote {path}: {len(words)} pre-tokens, {len(used)} of {tk._N_MERGES} merges ({os.path.getsize(path) / 1024:.1f} KiB)")
+
+
 def main():
     names = sys.argv[1:] or list(GENERATORS)
     for n in names:

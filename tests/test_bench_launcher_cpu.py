@@ -61,3 +61,36 @@ def test_single_rank_dry_run():
                        text=True, timeout=120)
     assert r.returncode == 0, r.stderr[-2000:]
     assert _json_line(r.stdout)["n_gpus"] == 1
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", BENCH)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_flags_parse():
+    bench = _bench_module()
+    a = bench.parse_args(["--steps", "7", "--warmup", "2", "--dump-outputs", "out"])
+    assert a.steps == 7 and a.warmup == 2 and a.dump_outputs == "out" and not a.full
+    assert bench.parse_args(["--full"]).full and bench.parse_args([]).dump_outputs is None
+
+
+def test_dump_outputs_writes_float32_and_a_fixed_sample(tmp_path):
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    n = bench.DUMP_MAX_ELEMENTS + 12345
+    big = torch.arange(n, dtype=torch.float32).view(1, -1)
+    out = {"pred_logits": torch.randn(1, 4, 7), "pred_masks": big, "pred_reid_logits": [None], "ids": torch.arange(3)}
+    bench.dump_outputs(out, str(tmp_path / "a"))
+    bench.dump_outputs(out, str(tmp_path / "b"))
+    assert sorted(os.listdir(tmp_path / "a")) == ["pred_logits.npy", "pred_masks_sample.npy"]
+    lg = np.load(tmp_path / "a" / "pred_logits.npy")
+    assert lg.dtype == np.float32 and np.array_equal(lg, out["pred_logits"].numpy())
+    s = np.load(tmp_path / "a" / "pred_masks_sample.npy")
+    assert s.dtype == np.float32 and s.shape == (bench.DUMP_MAX_ELEMENTS,)
+    assert np.all(np.diff(s) > 0) and s[-1] < n                 # distinct ascending flat indices of the source
+    assert np.array_equal(s, np.load(tmp_path / "b" / "pred_masks_sample.npy"))    # the same sample in every run

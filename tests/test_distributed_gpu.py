@@ -76,7 +76,7 @@ def test_frame_sharded_decoder_on_two_ranks_sharing_the_gpu(scenario):
 
 
 def test_bench_line_of_two_ranks_sharing_the_gpu():
-    """`bench.py --gpus 2` end to end with both ranks on GPU 0 (UNIVS_BENCH_ONE_GPU_DEBUG=1: gloo instead of RCCL, the times mean nothing):
+    """`bench.py --gpus 2 --full` end to end with both ranks on GPU 0 (UNIVS_BENCH_ONE_GPU_DEBUG=1: gloo instead of RCCL, the times mean nothing):
     the launcher, the replica step with its parity check against golden g12 on the timed output, the frame-sharded 10-frame clip and the
     sharded sliding loop run on the real kernels; the line keeps the reference within 1e-3 with no sign flip (0.097 / 16 flips before
     hazard 23 was cleared from the library)."""
@@ -86,7 +86,7 @@ def test_bench_line_of_two_ranks_sharing_the_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, UNIVS_BENCH_ONE_GPU_DEBUG="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"]
+           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"]
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

@@ -1,6 +1,8 @@
 """CPU: the CLIP tokenizer and text tower (univs_amd/modeling/language) against goldens of the REAL reference
-(oracle/gen_golden.py: g16a-c).  The tokenizer needs OpenAI CLIP's public merge table, which is data that is not shipped
-here: set UNIVS_BPE_VOCAB (the dev container finds the reference's copy); without it the tokenizer tests are skipped."""
+(oracle/gen_golden.py: g16a-c).  The tokenizer needs OpenAI CLIP's public merge table (MIT licence), which the package does
+not ship: the tests read tests/golden/bpe_merges_subset.txt.gz unless UNIVS_BPE_VOCAB names another table -- the full table
+cut down to the merges the tests' texts use, each at its own rank, so that ids and merges are the full table's
+(oracle/gen_golden.py: bpe_merges_subset)."""
 import os
 
 import numpy as np
@@ -10,12 +12,11 @@ import torch
 from oracle.cpu_path import cpu_ops
 from tests import cases
 
-_CANDIDATES = (os.environ.get("UNIVS_BPE_VOCAB"), "/root/reference/univs/modeling/language/bpe_simple_vocab_16e6.txt.gz")
-BPE = next((p for p in _CANDIDATES if p and os.path.isfile(p)), None)
-needs_vocab = pytest.mark.skipif(BPE is None, reason="CLIP BPE merge table not available")
+BPE = os.environ.get("UNIVS_BPE_VOCAB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                                                        "bpe_merges_subset.txt.gz")
+needs_vocab = pytest.mark.skipif(not os.path.isfile(BPE), reason="CLIP BPE merge table not available")
 
 
-@needs_vocab
 def test_tokenizer_matches_reference(golden_dir):
     from univs_amd.modeling.language import tokenizer as tk
     g = np.load(os.path.join(golden_dir, "g16a_tokenizer.npz"))
