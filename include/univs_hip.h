@@ -691,6 +691,47 @@ int univs_mask_stats_strided_f32(const float* x, long long outer, int inner, lon
  * ------------------------------------------------------------------------------------------- */
 int univs_token_mean_f32(const float* x, const float* add, int n, int L, int T, int C, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Per-image post-processing of mask logits without the upsampled stack (univs/inference/inference_image_generic_seg.py:214-431).
+ * The reference resizes all Q' logits L [Q', h, w] to the padded input size (Hp, Wp) first (:219-224: [333, 1024, 1024] fp32 at the
+ * shipped geometry) and then makes several full-size passes over it.  Here every entry evaluates U_q = bilinear(L_q -> Hp x Wp) on the
+ * fly (align_corners = false, ATen's source index and term order, as univs_bilinear_resample_f32), and none writes U.  The crop is
+ * rows [0, hi) x columns [0, wi) of U (the unpadded image, hi <= Hp, wi <= Wp).  `planes` [K] int32 selects planes of L (clamped to
+ * [0, Q')).  At most UNIVS_IMAGE_MAX_KEPT kept planes for the panoptic entries, 65 535 for the others; UNIVS_ERR_NOT_IMPLEMENTED
+ * beyond.
+ * ------------------------------------------------------------------------------------------- */
+#define UNIVS_IMAGE_MAX_KEPT 4096
+#define UNIVS_IMAGE_COVERED (1 << 30)
+
+/* out [Q', 8] int32, the univs_mask_stats_f32 record of U: {|U > 1|, |U > -1|} over the whole PADDED plane (the reference scores before
+ * the crop, :243), the box of {U > 0} over the crop, non-empty, 0.
+ * Replaces: calculate_mask_quality_scores (:243), convert_mask_to_box(mask_pred.gt(0)) (:363, :425) and the resize (:219-224). */
+int univs_image_mask_stats_f32(const float* logits, int Q, int h, int w, int Hp, int Wp, int hi, int wi, int32_t* out, void* stream);
+
+/* Over the crop: ids [hi, wi] int32 = k | (sigmoid(U_k) >= 0.5 ? UNIVS_IMAGE_COVERED : 0) for k = the FIRST maximum over the K kept planes
+ * of scores[k] * sigmoid(U_{planes[k]}) (argmax(0)); counts [K, 3] int32 (zeroed by the caller) += {|ids == k|, |sigmoid(U_k) >= 0.5|,
+ * |ids == k and covered|}.  sigmoid = 1 / (1 + exp(-x)) in fp32, compared after the sigmoid as the reference does.
+ * Replaces: panoptic_inference's sigmoid, score x mask, argmax and the per-segment sums (:318-353). */
+int univs_image_panoptic_ids_f32(const float* logits, int Q, int h, int w, int Hp, int Wp, int hi, int wi, const int32_t* planes,
+                                 const float* scores, int K, int32_t* ids, int32_t* counts, void* stream);
+
+/* out [H0, W0] int32 = covered ? lut[k] : 0 at the source pixel (min(floor(y * (hi / H0)), hi - 1), the same for x, in fp32) of ATen's
+ * nearest resize of ids [hi, wi]; seen [K] int32 (zeroed by the caller): 1 where a non-zero lut[k] reached the output.
+ * Replaces: the painting `panoptic_seg[mask] = id` (:360-379), the nearest resize and the `unique` of the segment ids (:255-262). */
+int univs_image_panoptic_paint_i32(const int32_t* ids, int hi, int wi, const int32_t* lut, int K, int H0, int W0, int32_t* out, int32_t* seen,
+                                   void* stream);
+
+/* out [C, hi, wi] float32 = sum over k < Qs (ascending, one fp32 fused multiply-add per term) of probs[k, c] * sigmoid(U_{planes[k]}).
+ * Replaces: semantic_inference's sigmoid + einsum("qc,qhw->chw") (:296-300). */
+int univs_image_semseg_f32(const float* logits, int Q, int h, int w, int Hp, int Wp, int hi, int wi, const int32_t* planes,
+                           const float* probs, int Qs, int C, float* out, void* stream);
+
+/* masks [N, H0, W0] uint8 = bilinear(crop(U_{planes[i]}) -> H0 x W0) > 0 (both resizes as ATen's, composed exactly); boxes [N, 8] int32:
+ * the record of univs_mask_stats_f32 with zero counts (left, top, right, bottom of the mask, non-empty).
+ * Replaces: instance_inference's second resize, the binarisation and convert_mask_to_box (:414-427). */
+int univs_image_instance_masks_u8(const float* logits, int Q, int h, int w, int Hp, int Wp, int hi, int wi, const int32_t* planes, int N,
+                                  int H0, int W0, uint8_t* masks, int32_t* boxes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -89,6 +89,11 @@ SIGNATURES = {
     "univs_mask_stats_f32": (_I, [_P, _c.c_longlong, _I, _I, _I, _I, _c.c_float, _c.c_float, _c.c_float, _P, _P]),
     "univs_mask_stats_strided_f32": (_I, [_P, _c.c_longlong, _I, _c.c_longlong, _c.c_longlong, _I, _I, _I, _I, _c.c_float, _c.c_float, _c.c_float, _P, _P]),
     "univs_prompt_tokens_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "univs_image_mask_stats_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "univs_image_panoptic_ids_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
+    "univs_image_panoptic_paint_i32": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
+    "univs_image_semseg_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
+    "univs_image_instance_masks_u8": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
 }
 
 _lib = None

@@ -117,7 +117,8 @@ def get_cfg():
                        TRANSFORMER_DECODER_NAME="VideoMultiScaleMaskedTransformerDecoderUniVS",
                        # mask2former/config.py:60-65, univs/config.py:90-91
                        TEST=CN(SEMANTIC_ON=True, INSTANCE_ON=False, PANOPTIC_ON=False, OBJECT_MASK_THRESHOLD=0.0,
-                               OVERLAP_THRESHOLD=0.0, STABILITY_SCORE_THRESH=0.0, OVERLAP_THRESHOLD_ENTITY=0.5))
+                               OVERLAP_THRESHOLD=0.0, STABILITY_SCORE_THRESH=0.0, OVERLAP_THRESHOLD_ENTITY=0.5,
+                               SEM_SEG_POSTPROCESSING_BEFORE_INFERENCE=False))
     m.BoxVIS = CN(TEST=CN(NUM_FRAMES=3, NUM_FRAMES_WINDOW=5, NUM_MAX_INST=50, CLIP_STRIDE=1,
                           LSJ_AUG_ENABLED=True, APPLY_CLS_THRES=0.05, MULTI_CLS_ON=True))   # univs/config.py:101-113
     # text tower of CLIP RN50x4 (TextEncoder.py:152-174 reads these; the reference sets them in its yaml recipes)
@@ -137,7 +138,7 @@ def get_cfg():
                       VIDEO_UNIFIED_INFERENCE_QUERIES="prompt", VIDEO_UNIFIED_INFERENCE_ENTITIES="",
                       BOX_NMS_THRESH=0.75, TEMPORAL_CONSISTENCY_THRESHOLD=0.05, DETECT_NEWLY_OBJECT_THRESHOLD=0.05,
                       CUSTOM_VIDEOS_ENABLE=False, CUSTOM_VIDEOS_TEXT=[],
-                      SEMANTIC_EXTRACTION=CN(ENABLE=False))
+                      SEMANTIC_EXTRACTION=CN(ENABLE=False), DISABLE_SEMANTIC_QUERIES=False)
     c.INPUT = CN(FORMAT="RGB", SAMPLING_FRAME_NUM=2, MIN_SIZE_TEST=800, MAX_SIZE_TEST=1333,
                  LSJ_AUG=CN(ENABLED=True, SQUARE_ENABLED=True, IMAGE_SIZE=1024, MIN_SCALE=0.25, MAX_SCALE=4.0))
     c.TEST = CN(DETECTIONS_PER_IMAGE=100)

@@ -74,6 +74,11 @@ int prompt_draw(const uint8_t*, const int*, const uint8_t*, const int*, const fl
                 int, long long*, long long*, uint8_t*, float*, hipStream_t);
 int prompt_point_pe_f32(const float*, const float*, const float*, const float*, float, int, int, int, float*, hipStream_t);
 int token_mean_f32(const float*, const float*, int, int, int, int, float*, hipStream_t);
+int image_mask_stats_f32(const float*, int, int, int, int, int, int, int, int*, hipStream_t);
+int image_panoptic_ids_f32(const float*, int, int, int, int, int, int, int, const int*, const float*, int, int*, int*, hipStream_t);
+int image_panoptic_paint_i32(const int*, int, int, const int*, int, int, int, int*, int*, hipStream_t);
+int image_semseg_f32(const float*, int, int, int, int, int, int, int, const int*, const float*, int, int, float*, hipStream_t);
+int image_instance_masks_u8(const float*, int, int, int, int, int, int, int, const int*, int, int, int, unsigned char*, int*, hipStream_t);
 int mask_stats_f32(const float*, long long, int, long long, long long, int, int, int, int, float, float, float, int*, hipStream_t);
 int prompt_tokens_f32(const float*, const long long*, const float*, const long long*, const float*, const float*, const long long*,
                       const uint8_t*, const uint8_t*, const float*, const long long*, int, int, int, int, int, int, int, float*, float*,
@@ -1007,6 +1012,101 @@ int univs_token_mean_f32(const float* x, const float* add, int n, int L, int T, 
     return UNIVS_ERR_NOT_IMPLEMENTED;
   }
   return rc;
+}
+
+// ---- per-image post-processing (csrc/image_post.hip) ----
+// the geometry every entry shares: L [Q, h, w] resized to (Hp, Wp), crop [0, hi) x [0, wi); a (Hp, Wp) below (h, w) is a
+// down-sampling, which the reference never asks for -- it is accepted all the same (the taps stay inside L)
+static bool image_geometry_ok(const char* what, int Q, int h, int w, int Hp, int Wp, int hi, int wi) {
+  if (Q < 1 || h < 1 || w < 1 || Hp < 1 || Wp < 1 || hi < 1 || wi < 1 || hi > Hp || wi > Wp || (long long)Hp * Wp > INT32_MAX ||
+      (long long)Q * h * w > (1LL << 40)) {
+    set_error("%s: bad geometry Q=%d low-res %dx%d padded %dx%d crop %dx%d", what, Q, h, w, Hp, Wp, hi, wi);
+    return false;
+  }
+  return true;
+}
+
+static int not_covered(const char* what, int rc, const char* limit) {
+  if (rc == UNIVS_ERR_NOT_IMPLEMENTED) set_error("%s: not covered (%s)", what, limit);
+  return rc;
+}
+
+int univs_image_mask_stats_f32(const float* logits, int Q, int h, int w, int Hp, int Wp, int hi, int wi, int32_t* out, void* stream) {
+  clear_sticky_error();
+  if (!image_geometry_ok("univs_image_mask_stats_f32", Q, h, w, Hp, Wp, hi, wi)) return UNIVS_ERR_INVALID_ARGUMENT;
+  if (!logits || !out) {
+    set_error("univs_image_mask_stats_f32: NULL data pointer");
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  return not_covered("univs_image_mask_stats_f32",
+                     image_mask_stats_f32(logits, Q, h, w, Hp, Wp, hi, wi, out, static_cast<hipStream_t>(stream)), "Q <= 65535");
+}
+
+int univs_image_panoptic_ids_f32(const float* logits, int Q, int h, int w, int Hp, int Wp, int hi, int wi, const int32_t* planes,
+                                 const float* scores, int K, int32_t* ids, int32_t* counts, void* stream) {
+  clear_sticky_error();
+  if (!image_geometry_ok("univs_image_panoptic_ids_f32", Q, h, w, Hp, Wp, hi, wi) || K < 1) {
+    if (K < 1) set_error("univs_image_panoptic_ids_f32: K=%d", K);
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  if (!logits || !planes || !scores || !ids || !counts) {
+    set_error("univs_image_panoptic_ids_f32: NULL data pointer");
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  return not_covered("univs_image_panoptic_ids_f32",
+                     image_panoptic_ids_f32(logits, Q, h, w, Hp, Wp, hi, wi, planes, scores, K, ids, counts, static_cast<hipStream_t>(stream)),
+                     "K <= UNIVS_IMAGE_MAX_KEPT");
+}
+
+int univs_image_panoptic_paint_i32(const int32_t* ids, int hi, int wi, const int32_t* lut, int K, int H0, int W0, int32_t* out, int32_t* seen,
+                                   void* stream) {
+  clear_sticky_error();
+  if (hi < 1 || wi < 1 || K < 1 || H0 < 1 || W0 < 1 || (long long)hi * wi > INT32_MAX || (long long)H0 * W0 > INT32_MAX) {
+    set_error("univs_image_panoptic_paint_i32: bad dimensions ids %dx%d K=%d out %dx%d", hi, wi, K, H0, W0);
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  if (!ids || !lut || !out || !seen) {
+    set_error("univs_image_panoptic_paint_i32: NULL data pointer");
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  return not_covered("univs_image_panoptic_paint_i32",
+                     image_panoptic_paint_i32(ids, hi, wi, lut, K, H0, W0, out, seen, static_cast<hipStream_t>(stream)),
+                     "K <= UNIVS_IMAGE_MAX_KEPT");
+}
+
+int univs_image_semseg_f32(const float* logits, int Q, int h, int w, int Hp, int Wp, int hi, int wi, const int32_t* planes,
+                           const float* probs, int Qs, int C, float* out, void* stream) {
+  clear_sticky_error();
+  if (!image_geometry_ok("univs_image_semseg_f32", Q, h, w, Hp, Wp, hi, wi) || Qs < 0 || C < 1) {
+    if (Qs < 0 || C < 1) set_error("univs_image_semseg_f32: Qs=%d C=%d", Qs, C);
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  if (!logits || !out || (Qs > 0 && (!planes || !probs))) {
+    set_error("univs_image_semseg_f32: NULL data pointer");
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  return not_covered("univs_image_semseg_f32",
+                     image_semseg_f32(logits, Q, h, w, Hp, Wp, hi, wi, planes, probs, Qs, C, out, static_cast<hipStream_t>(stream)),
+                     "C <= 65535 * 160");
+}
+
+int univs_image_instance_masks_u8(const float* logits, int Q, int h, int w, int Hp, int Wp, int hi, int wi, const int32_t* planes, int N,
+                                  int H0, int W0, uint8_t* masks, int32_t* boxes, void* stream) {
+  clear_sticky_error();
+  if (!image_geometry_ok("univs_image_instance_masks_u8", Q, h, w, Hp, Wp, hi, wi) || N < 0 || H0 < 1 || W0 < 1 ||
+      (long long)H0 * W0 > INT32_MAX) {
+    set_error("univs_image_instance_masks_u8: bad dimensions N=%d out %dx%d", N, H0, W0);
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  if (N == 0) return UNIVS_OK;
+  if (!logits || !planes || !masks || !boxes) {
+    set_error("univs_image_instance_masks_u8: NULL data pointer");
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  return not_covered("univs_image_instance_masks_u8",
+                     image_instance_masks_u8(logits, Q, h, w, Hp, Wp, hi, wi, planes, N, H0, W0, masks, boxes,
+                                             static_cast<hipStream_t>(stream)),
+                     "N <= 65535");
 }
 
 int univs_window_attention_image_f32(const float* qkv, const float* qkv_bias, const float* bias,

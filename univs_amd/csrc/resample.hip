@@ -14,32 +14,9 @@
 // Arithmetic follows ATen's kernel term by term (UpSampleBilinear2d.cu: area_pixel_compute_source_index,
 // h1p / w1p edge handling, the lambda products) so that results agree to rounding.
 #include "common.h"
+#include "resample_taps.h"
 
 namespace univs {
-
-struct Tap {
-  int i0, di;      // first tap, +1 or +0 (last row / column)
-  float l0, l1;    // weights
-};
-
-__device__ __forceinline__ Tap make_tap(float scale, int dst, int in_size) {
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  Tap t;
-  t.i0 = (int)src;
-  t.di = (t.i0 < in_size - 1) ? 1 : 0;
-  t.l1 = src - (float)t.i0;
-  t.l0 = 1.f - t.l1;
-  return t;
-}
-
-// l0y (l0x a + l1x b) + l1y (l0x c + l1x d) with the roundings spelled out (three products, three fused multiply-adds): left to the
-// compiler's contraction the two kernels below rounded the same expression differently
-__device__ __forceinline__ float bilerp(const Tap& ty, const Tap& tx, float a, float b, float c, float d) {
-  const float top = fmaf(tx.l1, b, tx.l0 * a);
-  const float bot = fmaf(tx.l1, d, tx.l0 * c);
-  return fmaf(ty.l1, bot, ty.l0 * top);
-}
 
 template <int VEC>
 __global__ __launch_bounds__(256) void bilinear_resample_f32_kernel(const float* __restrict__ in,

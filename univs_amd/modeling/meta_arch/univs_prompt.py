@@ -2,17 +2,19 @@
 back into (`model.backbone`, `model.sem_seg_head`, `model.prepare_targets`, `model.text_prompt_encoder`) and its
 `forward_inference` dispatch (:416-452):
 
+    image datasets ('coco*' / 'ade20k*')                        -> InferenceImageGenericSegmentation.eval
     task 'grounding' / 'sot', or custom text prompts            -> InferenceVideoVOS.eval
     category-specified tasks (ytvis / ovis / vipseg / vspw,
     or custom videos) with unified inference enabled             -> InferenceVideoEntity.eval
 
-The other branches of the reference (per-image COCO / ADE20k evaluation, the MinVIS / MDQE trackers of the non-unified
+The other branches of the reference (the MinVIS / MDQE trackers of the non-unified
 mode, EMA teacher weights, semantic-feature extraction, and all of training: losses, matcher, `forward` in train mode)
 are out of scope of the hot path and raise.
 """
 import torch
 from torch import nn
 
+from ...inference.image_generic_seg import InferenceImageGenericSegmentation
 from ...inference.video_entity import InferenceVideoEntity
 from ...inference.video_vos import InferenceVideoVOS
 from ...prepare_targets import PrepareTargets
@@ -25,7 +27,7 @@ class UniVS_Prompt(nn.Module):
     @configurable
     def __init__(self, *, backbone, sem_seg_head, prepare_targets, text_prompt_encoder, inference_video_entity,
                  inference_video_vos, pixel_mean, pixel_std, video_unified_inference_enable: bool,
-                 custom_videos_enable: bool, custom_videos_text):
+                 custom_videos_enable: bool, custom_videos_text, inference_img_generic_seg=None):
         super().__init__()
         self.backbone = backbone
         self.sem_seg_head = sem_seg_head
@@ -33,6 +35,7 @@ class UniVS_Prompt(nn.Module):
         self.text_prompt_encoder = text_prompt_encoder
         self.inference_video_entity = inference_video_entity
         self.inference_video_vos = inference_video_vos
+        self.inference_img_generic_seg = inference_img_generic_seg
         self.register_buffer("pixel_mean", torch.tensor(pixel_mean, dtype=torch.float32).view(-1, 1, 1), False)
         self.register_buffer("pixel_std", torch.tensor(pixel_std, dtype=torch.float32).view(-1, 1, 1), False)
         self.video_unified_inference_enable = video_unified_inference_enable
@@ -62,6 +65,7 @@ class UniVS_Prompt(nn.Module):
             "inference_video_vos": InferenceVideoVOS(cfg), "pixel_mean": cfg.MODEL.PIXEL_MEAN,
             "pixel_std": cfg.MODEL.PIXEL_STD, "video_unified_inference_enable": test.VIDEO_UNIFIED_INFERENCE_ENABLE,
             "custom_videos_enable": test.CUSTOM_VIDEOS_ENABLE, "custom_videos_text": test.CUSTOM_VIDEOS_TEXT,
+            "inference_img_generic_seg": InferenceImageGenericSegmentation(cfg),
         }
 
     @property
@@ -77,7 +81,9 @@ class UniVS_Prompt(nn.Module):
     def forward_inference(self, batched_inputs):
         name = batched_inputs[0]["dataset_name"]
         if name.startswith("coco") or name.startswith("ade20k"):
-            raise NotImplementedError("per-image evaluation (InferenceImageGenericSegmentation) is not built")
+            if self.inference_img_generic_seg is None:
+                raise NotImplementedError("per-image evaluation: this model was built without InferenceImageGenericSegmentation")
+            return self.inference_img_generic_seg.eval(self, batched_inputs)             # images (univs_prompt.py:420-426)
         if batched_inputs[0]["task"] in {"grounding", "sot"} or len(self.custom_videos_text):
             return self.inference_video_vos.eval(self, batched_inputs)          # prompt-specified tasks
         if self.video_unified_inference_enable or self.custom_videos_enable:

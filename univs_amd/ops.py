@@ -1378,6 +1378,142 @@ def mask_stats(x, t_hi=1.0, t_lo=-1.0, t_box=0.0, valid=None):
     return out
 
 
+
+# ---- per-image post-processing (include/univs_hip.h: univs_image_*; csrc/image_post.hip) ----------------------------------------------
+# L [Q', h, w] float32 low-resolution mask logits; `padded` = (Hp, Wp), the size the reference resizes them to; `crop` = (hi, wi), the
+# unpadded image inside it.  No kernel writes the resized stack.  Each wrapper returns None where the kernel does not cover the call
+# (grid / LDS limits, autograd), so that the caller keeps its ATen formulation.
+IMAGE_MAX_KEPT = 4096          # UNIVS_IMAGE_MAX_KEPT
+IMAGE_COVERED = 1 << 30        # UNIVS_IMAGE_COVERED: the covered bit of a panoptic id word
+
+
+def _image_args(name, L, padded, crop):
+    if not L.is_cuda:
+        raise RuntimeError(f"{name}: Not implemented on the CPU (tensor on {L.device}); the HIP extension is the only implementation")
+    if L.dtype != torch.float32 or L.dim() != 3:
+        raise RuntimeError(f"{name}: float32 [Q, h, w] logits only")
+    Hp, Wp = int(padded[0]), int(padded[1])
+    hi, wi = int(crop[0]), int(crop[1])
+    Q, h, w = (int(v) for v in L.shape)
+    if not (0 < hi <= Hp and 0 < wi <= Wp) or Q == 0 or h * w == 0:
+        raise RuntimeError(f"{name}: bad geometry L {tuple(L.shape)} padded {(Hp, Wp)} crop {(hi, wi)}")
+    if Hp * Wp >= 2 ** 31 or needs_grad(L):
+        return None
+    return L.contiguous(), Q, h, w, Hp, Wp, hi, wi
+
+
+def _planes_i32(planes, device):
+    return planes.to(device=device, dtype=torch.int32).contiguous()
+
+
+def image_mask_stats(L, padded, crop):
+    """int32 [Q', 8]: the `mask_stats` record of U = bilinear(L -> padded): (|U > 1|, |U > -1|) over the whole padded plane, the box of
+    {U > 0} over the crop (inclusive corners, zeros when empty), non-empty, 0 -- `calculate_mask_quality_scores` before the crop and
+    `convert_mask_to_box(crop(U) > 0)` (inference_image_generic_seg.py:243, :363).  None when not covered (Q' > 65 535)."""
+    a = _image_args("image_mask_stats", L, padded, crop)
+    if a is None or a[1] > 65535:
+        return None
+    L, Q, h, w, Hp, Wp, hi, wi = a
+    out = torch.empty((Q, 8), dtype=torch.int32, device=L.device)
+    with _on(L):
+        rc = _lib.load().univs_image_mask_stats_f32(_ptr(L), Q, h, w, Hp, Wp, hi, wi, _ptr(out), _stream_ptr(L))
+    if rc == _lib.ERR_NOT_IMPLEMENTED:
+        return None
+    _lib.check(rc, "image_mask_stats")
+    return out
+
+
+def image_panoptic_ids(L, padded, crop, planes, scores):
+    """Over the crop: ids int32 [hi, wi] = k | (IMAGE_COVERED if sigmoid(U_k) >= 0.5), k the FIRST maximum over the K kept planes of
+    scores[k] * sigmoid(U_{planes[k]}) (`argmax(0)`); counts int32 [K, 3] = (|ids == k|, |sigmoid(U_k) >= 0.5|, |ids == k, covered|)
+    (panoptic_inference, :318-353).  None when not covered (K > IMAGE_MAX_KEPT)."""
+    a = _image_args("image_panoptic_ids", L, padded, crop)
+    K = int(planes.numel())
+    if a is None or K == 0 or K > IMAGE_MAX_KEPT or int(scores.numel()) != K:
+        return None
+    L, Q, h, w, Hp, Wp, hi, wi = a
+    pl = _planes_i32(planes, L.device)
+    sc = scores.to(device=L.device, dtype=torch.float32).contiguous()
+    ids = torch.empty((hi, wi), dtype=torch.int32, device=L.device)
+    counts = torch.zeros((K, 3), dtype=torch.int32, device=L.device)
+    with _on(L):
+        rc = _lib.load().univs_image_panoptic_ids_f32(_ptr(L), Q, h, w, Hp, Wp, hi, wi, _ptr(pl), _ptr(sc), K, _ptr(ids), _ptr(counts),
+                                                      _stream_ptr(L))
+    if rc == _lib.ERR_NOT_IMPLEMENTED:
+        return None
+    _lib.check(rc, "image_panoptic_ids")
+    return ids, counts
+
+
+def image_panoptic_paint(ids, lut, out_size):
+    """out int32 [H0, W0] = covered ? lut[k] : 0, read through ATen's nearest resize of the [hi, wi] id words (`F.interpolate(...,
+    mode="nearest")`, :255-259); seen int32 [K]: 1 where a non-zero lut[k] reached the output.  None when not covered."""
+    if not ids.is_cuda:
+        raise RuntimeError(f"image_panoptic_paint: Not implemented on the CPU (tensor on {ids.device}); the HIP extension is the only implementation")
+    if ids.dtype != torch.int32 or ids.dim() != 2:
+        raise RuntimeError("image_panoptic_paint: int32 [hi, wi] ids only")
+    K = int(lut.numel())
+    H0, W0 = int(out_size[0]), int(out_size[1])
+    hi, wi = int(ids.shape[0]), int(ids.shape[1])
+    if K == 0 or K > IMAGE_MAX_KEPT or H0 * W0 >= 2 ** 31 or H0 < 1 or W0 < 1 or hi * wi == 0:
+        return None
+    ids = ids.contiguous()
+    lt = lut.to(device=ids.device, dtype=torch.int32).contiguous()
+    out = torch.empty((H0, W0), dtype=torch.int32, device=ids.device)
+    seen = torch.zeros(K, dtype=torch.int32, device=ids.device)
+    with _on(ids):
+        rc = _lib.load().univs_image_panoptic_paint_i32(_ptr(ids), hi, wi, _ptr(lt), K, H0, W0, _ptr(out), _ptr(seen), _stream_ptr(ids))
+    if rc == _lib.ERR_NOT_IMPLEMENTED:
+        return None
+    _lib.check(rc, "image_panoptic_paint")
+    return out, seen
+
+
+def image_semseg(L, padded, crop, planes, probs):
+    """float32 [C, hi, wi] = einsum("qc,qhw->chw", probs, sigmoid(crop(U_planes))) (semantic_inference, :296-300) with the sigmoid planes
+    made per tile and never stored; queries summed in ascending order, one fp32 rounding per term.  None when not covered."""
+    a = _image_args("image_semseg", L, padded, crop)
+    if a is None or needs_grad(probs) or probs.dim() != 2 or int(probs.shape[0]) != int(planes.numel()):
+        return None
+    L, Q, h, w, Hp, Wp, hi, wi = a
+    Qs, C = int(probs.shape[0]), int(probs.shape[1])
+    if C == 0 or (C + 159) // 160 > 65535:
+        return None
+    pl = _planes_i32(planes, L.device)
+    P = probs.to(device=L.device, dtype=torch.float32).contiguous()
+    out = torch.empty((C, hi, wi), dtype=torch.float32, device=L.device)
+    with _on(L):
+        rc = _lib.load().univs_image_semseg_f32(_ptr(L), Q, h, w, Hp, Wp, hi, wi, _ptr(pl) if Qs else None, _ptr(P) if Qs else None, Qs, C,
+                                                _ptr(out), _stream_ptr(L))
+    if rc == _lib.ERR_NOT_IMPLEMENTED:
+        return None
+    _lib.check(rc, "image_semseg")
+    return out
+
+
+def image_instance_masks(L, padded, crop, planes, out_size):
+    """uint8 [N, H0, W0] = bilinear(crop(U_planes) -> out_size) > 0 (instance_inference's second resize and binarisation, :414-422; both
+    resizes as ATen's) and int32 [N, 8] records of their boxes (left, top, right, bottom at [2:6], zeros when empty; :420).  None when not
+    covered (N > 65 535)."""
+    a = _image_args("image_instance_masks", L, padded, crop)
+    N = int(planes.numel())
+    H0, W0 = int(out_size[0]), int(out_size[1])
+    if a is None or N > 65535 or H0 < 1 or W0 < 1 or H0 * W0 >= 2 ** 31:
+        return None
+    L, Q, h, w, Hp, Wp, hi, wi = a
+    pl = _planes_i32(planes, L.device)
+    masks = torch.empty((N, H0, W0), dtype=torch.uint8, device=L.device)
+    boxes = torch.zeros((N, 8), dtype=torch.int32, device=L.device)
+    if N == 0:
+        return masks, boxes
+    with _on(L):
+        rc = _lib.load().univs_image_instance_masks_u8(_ptr(L), Q, h, w, Hp, Wp, hi, wi, _ptr(pl), N, H0, W0, _ptr(masks), _ptr(boxes),
+                                                       _stream_ptr(L))
+    if rc == _lib.ERR_NOT_IMPLEMENTED:
+        return None
+    _lib.check(rc, "image_instance_masks")
+    return masks, boxes
+
 def token_mean(x, add=None):
     """Mean over the non-blank tokens (univs_token_mean_f32): x [n, L, T, C] -> [n, T, C] = x.sum(1) / max(1, number of tokens l whose
     C channels are not all zero) (+ add [C]).  None when not covered."""

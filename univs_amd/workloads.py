@@ -3,6 +3,7 @@ product modules with the closed-form weights (univs_amd/synth.py).  One definiti
 tests (tests/cases.py and tests/helpers.py import these names), and -- through oracle/gen_golden.py, which feeds the very
 same tensors to the real reference -- by the golden fixtures.
 """
+import numpy as np
 import torch
 
 from . import synth
@@ -183,3 +184,26 @@ def build_model(device, case=None, variant=None, return_aux=False, **dec_over):
     """(backbone, head) of a workload on `device` with the closed-form weights: config 2 (Swin-T, 100 queries) by default."""
     case = CFG2 if case is None else case
     return build_swin(device, variant), build_head(case, device, return_aux=return_aux, **dec_over)
+
+
+# ---------------------------------------------------------------------------------------------------
+# per-image post-processing (inference/image_generic_seg.py): closed-form decoder outputs
+# ---------------------------------------------------------------------------------------------------
+def image_blob_logits(seed, Q, h, w, C, crop_lowres=None):
+    """Smooth mask logits L [Q, h, w] and class logits [Q, C] of one image from a seeded recipe (numpy's RandomState, so every machine
+    makes the same values): each query is -6 plus one to three Gaussian blobs (centres inside the low-resolution extent of the crop,
+    widths 1.5-8 cells, heights 4-12), so that masks overlap, win and lose pixels to each other and stuff classes repeat; class logits
+    are N(-2, 1.5^2) with a peak of 3-7 at one class per query (classes drawn from a third of the vocabulary, so that classes recur)."""
+    rs = np.random.RandomState(seed)
+    ch, cw = crop_lowres if crop_lowres is not None else (h, w)
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    L = np.full((Q, h, w), -6.0)
+    for q in range(Q):
+        for _ in range(rs.randint(1, 4)):
+            cy, cx = rs.uniform(0, ch), rs.uniform(0, cw)
+            s = rs.uniform(1.5, 8.0)
+            L[q] += rs.uniform(4.0, 12.0) * np.exp(-((yy - cy) ** 2 + (xx - cx) ** 2) / (2 * s * s))
+    cls = rs.normal(-2.0, 1.5, size=(Q, C))
+    peak = rs.randint(0, max(1, C // 3), size=Q) * 3 % C
+    cls[np.arange(Q), peak] += rs.uniform(3.0, 7.0, size=Q)
+    return torch.from_numpy(L.astype(np.float32)), torch.from_numpy(cls.astype(np.float32))
