@@ -732,6 +732,49 @@ int univs_image_semseg_f32(const float* logits, int Q, int h, int w, int Hp, int
 int univs_image_instance_masks_u8(const float* logits, int Q, int h, int w, int Hp, int Wp, int hi, int wi, const int32_t* planes, int N,
                                   int H0, int W0, uint8_t* masks, int32_t* boxes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Video post-processing of the MinVIS-style clip loop of the non-unified configs (csrc/video_post.hip;
+ * univs/inference/inference_video_vis_fast.py:219-351, univs/inference/inference_video_vps.py:209-406).
+ * The reference keeps every clip's [Q', T, h, w] mask logits in a list, averages each frame over the clips that cover it and resizes
+ * all selected masks of all frames to the padded input size before it counts and thresholds.  Here the clips go into one running sum
+ * S [Q', V, h, w] (V = video length) and, once S holds the per-frame mean M, every entry evaluates U_{q,v} = bilinear(M[q, v] -> Hp x
+ * Wp) on the fly (ATen's source index and term order, as univs_image_*); none writes U.  The crop is rows [0, hi) x columns [0, wi) of
+ * U.  `rows` [K] int32 selects rows q of M (clamped to [0, Q')).  UNIVS_ERR_NOT_IMPLEMENTED for shapes a kernel does not cover.
+ * ------------------------------------------------------------------------------------------- */
+
+/* S [Q, V, h, w] += M [Qm, T, h, w] gathered by perm [Q] int32 (clamped to [0, Qm)): S[q, i + t] += M[perm[q], t] for t < min(T, V - i).
+ * One writer per element; clips are added in order, so at T = 2 S * (1 / n_v) is the reference's two-term mean bit for bit.
+ * Replaces: the per-clip lists out_masks.append(pred_masks[indices]) and the stack-and-mean (vis_fast :271-297, vps :263-293). */
+int univs_minvis_accumulate_f32(float* S, int Q, int V, int h, int w, const float* M, int Qm, int T, const int32_t* perm, int i,
+                                void* stream);
+
+/* counts [K, 2] int32 (zeroed by the caller) += {|U > 1|, |U > -1|} over the CROP of frames 0, step, 2 step, ... of rows[k].
+ * Replaces: calculate_mask_quality_scores(mask_pred[:, ::itv]) after the resize and crop (vis_fast :326-328, vps :346-347). */
+int univs_video_mask_stats_f32(const float* M, int Q, int V, int h, int w, int Hp, int Wp, int hi, int wi, const int32_t* rows, int K,
+                               int step, int32_t* counts, void* stream);
+
+/* masks [N, V, H0, W0] uint8 = bilinear(crop(U_{rows[i], v}) -> H0 x W0) > 0 (both resizes as ATen's, composed exactly).
+ * Replaces: the per-row resize to the output size and the binarisation (vis_fast :330-339).  N V <= 65535. */
+int univs_video_instance_masks_u8(const float* M, int Q, int V, int h, int w, int Hp, int Wp, int hi, int wi, const int32_t* rows, int N,
+                                  int H0, int W0, uint8_t* masks, void* stream);
+
+/* ids [V, hi, wi] int32 over the crop = the FIRST k maximising scores[k] * sigmoid(U_{rows[k]}), -1 where sigmoid(U_k) < 0.5 for every k.
+ * Replaces: the sigmoid, is_bg, score x mask and argmax of inference_video_vps_save_results (vps :348-353). */
+int univs_video_panoptic_ids_i32(const float* M, int Q, int V, int h, int w, int Hp, int Wp, int hi, int wi, const int32_t* rows,
+                                 const float* scores, int K, int32_t* ids, void* stream);
+
+/* counts [K, 3] int32 (zeroed by the caller) += {|ids_o == k|, |p_k >= 0.5|, |ids_o == k and p_k >= 0.5|} over [V, H0, W0], where ids_o is
+ * the nearest resize of ids (ATen's source index: min(floor(y * (hi / H0)), hi - 1) in fp32) and p_k = bilinear(sigmoid(crop(U_k)) -> H0 x
+ * W0).  K <= UNIVS_IMAGE_MAX_KEPT, V H0 W0 < 2^31.
+ * Replaces: the nearest resize of the ids, the per-k resize of the probabilities and the three areas per k (vps :354-369). */
+int univs_video_panoptic_counts_i32(const float* M, int Q, int V, int h, int w, int Hp, int Wp, int hi, int wi, const int32_t* rows, int K,
+                                    const int32_t* ids, int H0, int W0, int32_t* counts, void* stream);
+
+/* out [V, H0, W0] int32 = lut[k] where ids_o == k and p_k >= 0.5 (as univs_video_panoptic_counts_i32), else 0.
+ * Replaces: panoptic_seg[mask] = id (vps :371-386). */
+int univs_video_panoptic_paint_i32(const float* M, int Q, int V, int h, int w, int Hp, int Wp, int hi, int wi, const int32_t* rows, int K,
+                                   const int32_t* ids, const int32_t* lut, int H0, int W0, int32_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,6 +94,12 @@ SIGNATURES = {
     "univs_image_panoptic_paint_i32": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
     "univs_image_semseg_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
     "univs_image_instance_masks_u8": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
+    "univs_minvis_accumulate_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P]),
+    "univs_video_mask_stats_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P]),
+    "univs_video_instance_masks_u8": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P]),
+    "univs_video_panoptic_ids_i32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P]),
+    "univs_video_panoptic_counts_i32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P]),
+    "univs_video_panoptic_paint_i32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P]),
 }
 
 _lib = None

@@ -120,7 +120,9 @@ def get_cfg():
                                OVERLAP_THRESHOLD=0.0, STABILITY_SCORE_THRESH=0.0, OVERLAP_THRESHOLD_ENTITY=0.5,
                                SEM_SEG_POSTPROCESSING_BEFORE_INFERENCE=False))
     m.BoxVIS = CN(TEST=CN(NUM_FRAMES=3, NUM_FRAMES_WINDOW=5, NUM_MAX_INST=50, CLIP_STRIDE=1,
-                          LSJ_AUG_ENABLED=True, APPLY_CLS_THRES=0.05, MULTI_CLS_ON=True))   # univs/config.py:101-113
+                          LSJ_AUG_ENABLED=True, APPLY_CLS_THRES=0.05, MULTI_CLS_ON=True,
+                          ZERO_SHOT_INFERENCE=False, TRACKER_TYPE="minvis", WINDOW_INFERENCE=False,
+                          MERGE_ON_CPU=False))   # univs/config.py:101-113
     # text tower of CLIP RN50x4 (TextEncoder.py:152-174 reads these; the reference sets them in its yaml recipes)
     m.CLIP = CN(RESNETS_DEPTH=200, BACKBONE_FREEZE_AT=0, WEIGHTS="")
     m.UniVS = CN(PROMPT_TYPE="category",

@@ -80,6 +80,13 @@ int image_panoptic_paint_i32(const int*, int, int, const int*, int, int, int, in
 int image_semseg_f32(const float*, int, int, int, int, int, int, int, const int*, const float*, int, int, float*, hipStream_t);
 int image_instance_masks_u8(const float*, int, int, int, int, int, int, int, const int*, int, int, int, unsigned char*, int*, hipStream_t);
 int mask_stats_f32(const float*, long long, int, long long, long long, int, int, int, int, float, float, float, int*, hipStream_t);
+int minvis_accumulate_f32(float*, int, int, int, int, const float*, int, int, const int*, int, hipStream_t);
+int video_mask_stats_f32(const float*, int, int, int, int, int, int, int, int, const int*, int, int, int*, hipStream_t);
+int video_instance_masks_u8(const float*, int, int, int, int, int, int, int, int, const int*, int, int, int, unsigned char*, hipStream_t);
+int video_panoptic_ids_i32(const float*, int, int, int, int, int, int, int, int, const int*, const float*, int, int*, hipStream_t);
+int video_panoptic_counts_i32(const float*, int, int, int, int, int, int, int, int, const int*, int, const int*, int, int, int*, hipStream_t);
+int video_panoptic_paint_i32(const float*, int, int, int, int, int, int, int, int, const int*, int, const int*, const int*, int, int, int*,
+                             hipStream_t);
 int prompt_tokens_f32(const float*, const long long*, const float*, const long long*, const float*, const float*, const long long*,
                       const uint8_t*, const uint8_t*, const float*, const long long*, int, int, int, int, int, int, int, float*, float*,
                       uint8_t*, hipStream_t);
@@ -1107,6 +1114,112 @@ int univs_image_instance_masks_u8(const float* logits, int Q, int h, int w, int 
                      image_instance_masks_u8(logits, Q, h, w, Hp, Wp, hi, wi, planes, N, H0, W0, masks, boxes,
                                              static_cast<hipStream_t>(stream)),
                      "N <= 65535");
+}
+
+// ---- video post-processing of the MinVIS-style clip loop (csrc/video_post.hip) ----
+static bool video_geometry_ok(const char* what, int Q, int V, int h, int w, int Hp, int Wp, int hi, int wi) {
+  if (V < 1 || !image_geometry_ok(what, Q, h, w, Hp, Wp, hi, wi) || (long long)Q * V * h * w > (1LL << 40) ||
+      (long long)V * hi * wi > INT32_MAX) {
+    set_error("%s: bad geometry Q=%d V=%d low-res %dx%d padded %dx%d crop %dx%d", what, Q, V, h, w, Hp, Wp, hi, wi);
+    return false;
+  }
+  return true;
+}
+
+int univs_minvis_accumulate_f32(float* S, int Q, int V, int h, int w, const float* M, int Qm, int T, const int32_t* perm, int i,
+                                void* stream) {
+  clear_sticky_error();
+  if (Q < 0 || V < 1 || h < 1 || w < 1 || Qm < 1 || T < 1 || i < 0 || i >= V || (long long)Q * V * h * w > (1LL << 40) ||
+      (long long)Qm * T * h * w > (1LL << 40)) {
+    set_error("univs_minvis_accumulate_f32: bad dimensions Q=%d V=%d %dx%d Qm=%d T=%d i=%d", Q, V, h, w, Qm, T, i);
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  if (Q == 0) return UNIVS_OK;
+  if (!S || !M || !perm) {
+    set_error("univs_minvis_accumulate_f32: NULL data pointer");
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  return minvis_accumulate_f32(S, Q, V, h, w, M, Qm, T, perm, i, static_cast<hipStream_t>(stream));
+}
+
+int univs_video_mask_stats_f32(const float* M, int Q, int V, int h, int w, int Hp, int Wp, int hi, int wi, const int32_t* rows, int K,
+                               int step, int32_t* counts, void* stream) {
+  clear_sticky_error();
+  if (!video_geometry_ok("univs_video_mask_stats_f32", Q, V, h, w, Hp, Wp, hi, wi) || K < 0 || step < 1) {
+    if (K < 0 || step < 1) set_error("univs_video_mask_stats_f32: K=%d step=%d", K, step);
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  if (K == 0) return UNIVS_OK;
+  if (!M || !rows || !counts) {
+    set_error("univs_video_mask_stats_f32: NULL data pointer");
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  return not_covered("univs_video_mask_stats_f32",
+                     video_mask_stats_f32(M, Q, V, h, w, Hp, Wp, hi, wi, rows, K, step, counts, static_cast<hipStream_t>(stream)),
+                     "K <= 65535, sampled frames x crop < 2^31");
+}
+
+int univs_video_instance_masks_u8(const float* M, int Q, int V, int h, int w, int Hp, int Wp, int hi, int wi, const int32_t* rows, int N,
+                                  int H0, int W0, uint8_t* masks, void* stream) {
+  clear_sticky_error();
+  if (!video_geometry_ok("univs_video_instance_masks_u8", Q, V, h, w, Hp, Wp, hi, wi) || N < 0 || H0 < 1 || W0 < 1 ||
+      (long long)H0 * W0 > INT32_MAX) {
+    set_error("univs_video_instance_masks_u8: bad dimensions N=%d out %dx%d", N, H0, W0);
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  if (N == 0) return UNIVS_OK;
+  if (!M || !rows || !masks) {
+    set_error("univs_video_instance_masks_u8: NULL data pointer");
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  return not_covered("univs_video_instance_masks_u8",
+                     video_instance_masks_u8(M, Q, V, h, w, Hp, Wp, hi, wi, rows, N, H0, W0, masks, static_cast<hipStream_t>(stream)),
+                     "N V <= 65535");
+}
+
+int univs_video_panoptic_ids_i32(const float* M, int Q, int V, int h, int w, int Hp, int Wp, int hi, int wi, const int32_t* rows,
+                                 const float* scores, int K, int32_t* ids, void* stream) {
+  clear_sticky_error();
+  if (!video_geometry_ok("univs_video_panoptic_ids_i32", Q, V, h, w, Hp, Wp, hi, wi) || K < 1) {
+    if (K < 1) set_error("univs_video_panoptic_ids_i32: K=%d", K);
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  if (!M || !rows || !scores || !ids) {
+    set_error("univs_video_panoptic_ids_i32: NULL data pointer");
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  return video_panoptic_ids_i32(M, Q, V, h, w, Hp, Wp, hi, wi, rows, scores, K, ids, static_cast<hipStream_t>(stream));
+}
+
+int univs_video_panoptic_counts_i32(const float* M, int Q, int V, int h, int w, int Hp, int Wp, int hi, int wi, const int32_t* rows, int K,
+                                    const int32_t* ids, int H0, int W0, int32_t* counts, void* stream) {
+  clear_sticky_error();
+  if (!video_geometry_ok("univs_video_panoptic_counts_i32", Q, V, h, w, Hp, Wp, hi, wi) || K < 1 || H0 < 1 || W0 < 1) {
+    set_error("univs_video_panoptic_counts_i32: bad dimensions K=%d out %dx%d", K, H0, W0);
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  if (!M || !rows || !ids || !counts) {
+    set_error("univs_video_panoptic_counts_i32: NULL data pointer");
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  return not_covered("univs_video_panoptic_counts_i32",
+                     video_panoptic_counts_i32(M, Q, V, h, w, Hp, Wp, hi, wi, rows, K, ids, H0, W0, counts, static_cast<hipStream_t>(stream)),
+                     "K <= UNIVS_IMAGE_MAX_KEPT, V H0 W0 < 2^31");
+}
+
+int univs_video_panoptic_paint_i32(const float* M, int Q, int V, int h, int w, int Hp, int Wp, int hi, int wi, const int32_t* rows, int K,
+                                   const int32_t* ids, const int32_t* lut, int H0, int W0, int32_t* out, void* stream) {
+  clear_sticky_error();
+  if (!video_geometry_ok("univs_video_panoptic_paint_i32", Q, V, h, w, Hp, Wp, hi, wi) || K < 1 || H0 < 1 || W0 < 1 ||
+      (long long)V * H0 * W0 > (1LL << 40)) {
+    set_error("univs_video_panoptic_paint_i32: bad dimensions K=%d out %dx%d", K, H0, W0);
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  if (!M || !rows || !ids || !lut || !out) {
+    set_error("univs_video_panoptic_paint_i32: NULL data pointer");
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  return video_panoptic_paint_i32(M, Q, V, h, w, Hp, Wp, hi, wi, rows, K, ids, lut, H0, W0, out, static_cast<hipStream_t>(stream));
 }
 
 int univs_window_attention_image_f32(const float* qkv, const float* qkv_bias, const float* bias,

@@ -35,15 +35,6 @@ struct Plane {
   float rh, rw;    // (float) h / Hp, (float) w / Wp: ATen's area_pixel_compute_scale without align_corners
 };
 
-__device__ __forceinline__ float u_at(const float* __restrict__ plane, int w, const Tap& ty, const Tap& tx) {
-  const float* r0 = plane + (long long)ty.i0 * w;
-  const float* r1 = r0 + (long long)ty.di * w;
-  return bilerp(ty, tx, r0[tx.i0], r0[tx.i0 + tx.di], r1[tx.i0], r1[tx.i0 + tx.di]);
-}
-
-// ATen's sigmoid kernel: 1 / (1 + exp(-x)) in fp32, correctly rounded division
-__device__ __forceinline__ float sigmoid_f32(float x) { return 1.f / (1.f + expf(-x)); }
-
 __device__ __forceinline__ const float* plane_ptr(const float* L, const int* __restrict__ planes, int k, int Q, long long hw) {
   int q = planes[k];
   q = q < 0 ? 0 : (q >= Q ? Q - 1 : q);

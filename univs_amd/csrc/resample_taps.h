@@ -1,5 +1,5 @@
-// Bilinear taps (align_corners = false) shared by the resampling kernels (resample.hip) and the image post-processing kernels
-// (image_post.hip): ATen's area_pixel_compute_source_index, h1p / w1p edge handling and the lambda products, term by term.
+// Bilinear taps (align_corners = false) shared by the resampling kernels (resample.hip) and the post-processing kernels
+// (image_post.hip, video_post.hip): ATen's area_pixel_compute_source_index, h1p / w1p edge handling and the lambda products, term by term.
 #pragma once
 #include "common.h"
 
@@ -28,5 +28,15 @@ __device__ __forceinline__ float bilerp(const Tap& ty, const Tap& tx, float a, f
   const float bot = fmaf(tx.l1, d, tx.l0 * c);
   return fmaf(ty.l1, bot, ty.l0 * top);
 }
+
+// U(y, x) of one plane [h, w] of L from its taps (the post-processing kernels: image_post.hip, video_post.hip)
+__device__ __forceinline__ float u_at(const float* __restrict__ plane, int w, const Tap& ty, const Tap& tx) {
+  const float* r0 = plane + (long long)ty.i0 * w;
+  const float* r1 = r0 + (long long)ty.di * w;
+  return bilerp(ty, tx, r0[tx.i0], r0[tx.i0 + tx.di], r1[tx.i0], r1[tx.i0 + tx.di]);
+}
+
+// ATen's sigmoid kernel: 1 / (1 + exp(-x)) in fp32, correctly rounded division
+__device__ __forceinline__ float sigmoid_f32(float x) { return 1.f / (1.f + expf(-x)); }
 
 }  // namespace univs

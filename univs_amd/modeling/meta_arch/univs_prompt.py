@@ -6,16 +6,19 @@ back into (`model.backbone`, `model.sem_seg_head`, `model.prepare_targets`, `mod
     task 'grounding' / 'sot', or custom text prompts            -> InferenceVideoVOS.eval
     category-specified tasks (ytvis / ovis / vipseg / vspw,
     or custom videos) with unified inference enabled             -> InferenceVideoEntity.eval
+    unified inference disabled: 'ytvis*' / 'ovis*' with
+    TRACKER_TYPE 'minvis'                                        -> InferenceVideoVISFast.eval
+    unified inference disabled: 'vipseg*' / 'vpsw*'              -> InferenceVideoVPS.eval (which serves 'vipseg*' only)
 
-The other branches of the reference (the MinVIS / MDQE trackers of the non-unified
-mode, EMA teacher weights, semantic-feature extraction, and all of training: losses, matcher, `forward` in train mode)
-are out of scope of the hot path and raise.
+The other branches of the reference (the MDQE tracker of the non-unified mode, EMA teacher weights, semantic-feature
+extraction, and all of training: losses, matcher, `forward` in train mode) are out of scope of the hot path and raise.
 """
 import torch
 from torch import nn
 
 from ...inference.image_generic_seg import InferenceImageGenericSegmentation
 from ...inference.video_entity import InferenceVideoEntity
+from ...inference.video_minvis import InferenceVideoVISFast, InferenceVideoVPS
 from ...inference.video_vos import InferenceVideoVOS
 from ...prepare_targets import PrepareTargets
 from ...registry import META_ARCH_REGISTRY, configurable
@@ -27,7 +30,8 @@ class UniVS_Prompt(nn.Module):
     @configurable
     def __init__(self, *, backbone, sem_seg_head, prepare_targets, text_prompt_encoder, inference_video_entity,
                  inference_video_vos, pixel_mean, pixel_std, video_unified_inference_enable: bool,
-                 custom_videos_enable: bool, custom_videos_text, inference_img_generic_seg=None):
+                 custom_videos_enable: bool, custom_videos_text, inference_img_generic_seg=None, inference_video_vis_fast=None,
+                 inference_video_vps=None, tracker_type: str = "minvis"):
         super().__init__()
         self.backbone = backbone
         self.sem_seg_head = sem_seg_head
@@ -36,6 +40,9 @@ class UniVS_Prompt(nn.Module):
         self.inference_video_entity = inference_video_entity
         self.inference_video_vos = inference_video_vos
         self.inference_img_generic_seg = inference_img_generic_seg
+        self.inference_video_vis_fast = inference_video_vis_fast
+        self.inference_video_vps = inference_video_vps
+        self.tracker_type = tracker_type
         self.register_buffer("pixel_mean", torch.tensor(pixel_mean, dtype=torch.float32).view(-1, 1, 1), False)
         self.register_buffer("pixel_std", torch.tensor(pixel_std, dtype=torch.float32).view(-1, 1, 1), False)
         self.video_unified_inference_enable = video_unified_inference_enable
@@ -66,6 +73,8 @@ class UniVS_Prompt(nn.Module):
             "pixel_std": cfg.MODEL.PIXEL_STD, "video_unified_inference_enable": test.VIDEO_UNIFIED_INFERENCE_ENABLE,
             "custom_videos_enable": test.CUSTOM_VIDEOS_ENABLE, "custom_videos_text": test.CUSTOM_VIDEOS_TEXT,
             "inference_img_generic_seg": InferenceImageGenericSegmentation(cfg),
+            "inference_video_vis_fast": InferenceVideoVISFast(cfg), "inference_video_vps": InferenceVideoVPS(cfg),
+            "tracker_type": cfg.MODEL.BoxVIS.TEST.TRACKER_TYPE,
         }
 
     @property
@@ -90,15 +99,34 @@ class UniVS_Prompt(nn.Module):
             if name.startswith(("ytvis", "ovis", "vipseg", "vspw")) or self.custom_videos_enable:
                 return self.inference_video_entity.eval(self, batched_inputs)   # category-specified tasks
             raise ValueError(f"Not support to eval the dataset {name} yet")
-        raise NotImplementedError("the non-unified trackers (MinVIS / MDQE style association) are not built: set "
-                                  "MODEL.UniVS.TEST.VIDEO_UNIFIED_INFERENCE_ENABLE True")
+        return self.non_unified_inference(batched_inputs)
+
+    def non_unified_inference(self, batched_inputs):
+        """The non-unified branches (univs_prompt.py:443-451): MinVIS-style VIS for 'ytvis*' / 'ovis*', online VPS for 'vipseg*' /
+        'vpsw*' (the reference's spelling; its VPS driver serves 'vipseg*' only and raises for the others)."""
+        name = batched_inputs[0]["dataset_name"]
+        if name.startswith(("ytvis", "ovis")):
+            if self.tracker_type == "mdqe":
+                raise NotImplementedError("the MDQE over-tracker (MODEL.BoxVIS.TEST.TRACKER_TYPE 'mdqe') is not built: use TRACKER_TYPE "
+                                          "'minvis'")
+            return self._driver("inference_video_vis_fast").eval(self, batched_inputs)
+        if name.startswith(("vipseg", "vpsw")):
+            return self._driver("inference_video_vps").eval(self, batched_inputs)
+        raise ValueError(f"Not support to eval the dataset {name} yet")
+
+    def _driver(self, attr):
+        d = getattr(self, attr, None)
+        if d is None:
+            raise NotImplementedError(f"non-unified video inference: this model was built without {attr}")
+        return d
 
 
 @META_ARCH_REGISTRY.register()
 class UniVS_Prompt_LongVideo(UniVS_Prompt):
     """`univs/univs_prompt_longvideo.py`: the long-video recipe differs from `UniVS_Prompt` in TRAINING only (several clips
     of one video per step, inter-clip re-identification loss, :347-438 / :469-589); its inference dispatch (:440-467) sends
-    category-specified videos to the same unified entity loop and 'sot*' datasets to the VOS loop."""
+    category-specified videos to the same unified entity loop, or with unified inference disabled to the same MinVIS-style
+    drivers, and 'sot*' datasets to the VOS loop."""
 
     @torch.no_grad()
     def forward_inference(self, batched_inputs):
@@ -111,8 +139,7 @@ class UniVS_Prompt_LongVideo(UniVS_Prompt):
             raise ValueError(f"Not support to eval the dataset {name} yet")
         if name.startswith("sot"):
             return self.inference_video_vos.eval(self, batched_inputs)
-        raise NotImplementedError("the non-unified trackers (MinVIS / MDQE style association) are not built: set "
-                                  "MODEL.UniVS.TEST.VIDEO_UNIFIED_INFERENCE_ENABLE True")
+        return self.non_unified_inference(batched_inputs)
 
 
 @META_ARCH_REGISTRY.register()

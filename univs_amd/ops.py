@@ -1721,3 +1721,153 @@ def msda_prepare(proj, n_off, reference_points, spatial_shapes, num_heads, num_l
                                                _ptr(loc), _ptr(attn), _stream_ptr(proj))
     _lib.check(rc, "msda_prepare")
     return loc, attn
+
+
+# ---- video post-processing of the MinVIS-style clip loop (csrc/video_post.hip) ----------------------------------------------------------
+def minvis_accumulate(S, M, perm, i):
+    """In place: S [Q', V, h, w] float32 += the clip's masks M [Qm, T, h, w] in the matched order, S[q, i + t] += M[perm[q], t] for t <
+    min(T, V - i) (the running sum that replaces the per-clip mask list of inference_video_vis_fast.py:271-297 / inference_video_vps.py:
+    263-293).  One writer per element; clips added in order.  Returns S."""
+    for name, t in (("S", S), ("M", M)):
+        if not t.is_cuda:
+            raise RuntimeError(f"minvis_accumulate: Not implemented on the CPU ({name} on {t.device}); the HIP extension is the only implementation")
+        if t.dtype != torch.float32 or t.dim() != 4:
+            raise RuntimeError(f"minvis_accumulate: float32 4-d {name} only")
+    if not S.is_contiguous():
+        raise RuntimeError("minvis_accumulate: S must be contiguous (it is updated in place)")
+    Q, V, h, w = (int(v) for v in S.shape)
+    Qm, T = int(M.shape[0]), int(M.shape[1])
+    if tuple(M.shape[2:]) != (h, w) or int(perm.numel()) != Q or not 0 <= int(i) < V:
+        raise RuntimeError(f"minvis_accumulate: S {tuple(S.shape)}, M {tuple(M.shape)}, perm {int(perm.numel())}, i {i}")
+    M = M.contiguous()
+    pm = _planes_i32(perm, S.device)
+    with _on(S):
+        rc = _lib.load().univs_minvis_accumulate_f32(_ptr(S), Q, V, h, w, _ptr(M), Qm, T, _ptr(pm), int(i), _stream_ptr(S))
+    _lib.check(rc, "minvis_accumulate")
+    return S
+
+
+def _video_args(name, M, padded, crop):
+    if not M.is_cuda:
+        raise RuntimeError(f"{name}: Not implemented on the CPU (tensor on {M.device}); the HIP extension is the only implementation")
+    if M.dtype != torch.float32 or M.dim() != 4:
+        raise RuntimeError(f"{name}: float32 [Q, V, h, w] mask logits only")
+    Hp, Wp = int(padded[0]), int(padded[1])
+    hi, wi = int(crop[0]), int(crop[1])
+    Q, V, h, w = (int(v) for v in M.shape)
+    if not (0 < hi <= Hp and 0 < wi <= Wp) or Q * V == 0 or h * w == 0:
+        raise RuntimeError(f"{name}: bad geometry M {tuple(M.shape)} padded {(Hp, Wp)} crop {(hi, wi)}")
+    if Hp * Wp >= 2 ** 31 or V * hi * wi >= 2 ** 31 or needs_grad(M):
+        return None
+    return M.contiguous(), Q, V, h, w, Hp, Wp, hi, wi
+
+
+def video_mask_stats(M, padded, crop, rows, step):
+    """int32 [K, 2] = (|U > 1|, |U > -1|) of rows[k] over the crop of frames 0, step, 2 step, ... (calculate_mask_quality_scores(
+    mask_pred[:, ::step]) after the resize and crop: inference_video_vis_fast.py:326-328, inference_video_vps.py:346-347).  None when not
+    covered."""
+    a = _video_args("video_mask_stats", M, padded, crop)
+    K = int(rows.numel())
+    if a is None or K > 65535 or int(step) < 1:
+        return None
+    M, Q, V, h, w, Hp, Wp, hi, wi = a
+    counts = torch.zeros((K, 2), dtype=torch.int32, device=M.device)
+    if K == 0:
+        return counts
+    r = _planes_i32(rows, M.device)
+    with _on(M):
+        rc = _lib.load().univs_video_mask_stats_f32(_ptr(M), Q, V, h, w, Hp, Wp, hi, wi, _ptr(r), K, int(step), _ptr(counts), _stream_ptr(M))
+    if rc == _lib.ERR_NOT_IMPLEMENTED:
+        return None
+    _lib.check(rc, "video_mask_stats")
+    return counts
+
+
+def video_instance_masks(M, padded, crop, rows, out_size, out=None):
+    """uint8 [N, V, H0, W0] = bilinear(crop(U_{rows[i], v}) -> out_size) > 0 (inference_video_vis_fast.py:330-339; both resizes as ATen's).
+    `out`: an optional uint8 tensor of that shape to write into.  None when not covered (N V > 65 535)."""
+    a = _video_args("video_instance_masks", M, padded, crop)
+    N = int(rows.numel())
+    H0, W0 = int(out_size[0]), int(out_size[1])
+    if a is None or H0 < 1 or W0 < 1 or H0 * W0 >= 2 ** 31:
+        return None
+    M, Q, V, h, w, Hp, Wp, hi, wi = a
+    if N * V > 65535:
+        return None
+    masks = torch.empty((N, V, H0, W0), dtype=torch.uint8, device=M.device) if out is None else out
+    if tuple(masks.shape) != (N, V, H0, W0) or masks.dtype != torch.uint8 or not masks.is_contiguous():
+        raise RuntimeError(f"video_instance_masks: out {tuple(masks.shape)} {masks.dtype}, expected contiguous uint8 {(N, V, H0, W0)}")
+    if N == 0:
+        return masks
+    r = _planes_i32(rows, M.device)
+    with _on(M):
+        rc = _lib.load().univs_video_instance_masks_u8(_ptr(M), Q, V, h, w, Hp, Wp, hi, wi, _ptr(r), N, H0, W0, _ptr(masks), _stream_ptr(M))
+    if rc == _lib.ERR_NOT_IMPLEMENTED:
+        return None
+    _lib.check(rc, "video_instance_masks")
+    return masks
+
+
+def video_panoptic_ids(M, padded, crop, rows, scores):
+    """int32 [V, hi, wi] over the crop: the FIRST k maximising scores[k] * sigmoid(U_{rows[k]}), -1 where sigmoid(U_k) < 0.5 for every k
+    (inference_video_vps.py:348-353).  None when not covered."""
+    a = _video_args("video_panoptic_ids", M, padded, crop)
+    K = int(rows.numel())
+    if a is None or K == 0 or int(scores.numel()) != K:
+        return None
+    M, Q, V, h, w, Hp, Wp, hi, wi = a
+    r = _planes_i32(rows, M.device)
+    sc = scores.to(device=M.device, dtype=torch.float32).contiguous()
+    ids = torch.empty((V, hi, wi), dtype=torch.int32, device=M.device)
+    with _on(M):
+        rc = _lib.load().univs_video_panoptic_ids_i32(_ptr(M), Q, V, h, w, Hp, Wp, hi, wi, _ptr(r), _ptr(sc), K, _ptr(ids), _stream_ptr(M))
+    if rc == _lib.ERR_NOT_IMPLEMENTED:
+        return None
+    _lib.check(rc, "video_panoptic_ids")
+    return ids
+
+
+def _video_out_args(name, M, padded, crop, rows, ids, out_size):
+    a = _video_args(name, M, padded, crop)
+    K = int(rows.numel())
+    H0, W0 = int(out_size[0]), int(out_size[1])
+    if a is None or K == 0 or K > IMAGE_MAX_KEPT or H0 < 1 or W0 < 1 or a[2] * H0 * W0 >= 2 ** 31:
+        return None
+    if ids.dtype != torch.int32 or tuple(ids.shape) != (a[2], a[7], a[8]) or ids.device != M.device:
+        raise RuntimeError(f"{name}: ids {tuple(ids.shape)} {ids.dtype}, expected int32 {(a[2], a[7], a[8])} on {M.device}")
+    return a, _planes_i32(rows, M.device), K, H0, W0
+
+
+def video_panoptic_counts(M, padded, crop, rows, ids, out_size):
+    """int32 [K, 3] = (|ids_o == k|, |p_k >= 0.5|, |ids_o == k and p_k >= 0.5|) over [V, H0, W0]: ids_o the nearest resize of `ids` (ATen's
+    rule), p_k = bilinear(sigmoid(crop(U_{rows[k]})) -> out_size) (inference_video_vps.py:354-369).  None when not covered."""
+    b = _video_out_args("video_panoptic_counts", M, padded, crop, rows, ids, out_size)
+    if b is None:
+        return None
+    (M, Q, V, h, w, Hp, Wp, hi, wi), r, K, H0, W0 = b
+    counts = torch.zeros((K, 3), dtype=torch.int32, device=M.device)
+    with _on(M):
+        rc = _lib.load().univs_video_panoptic_counts_i32(_ptr(M), Q, V, h, w, Hp, Wp, hi, wi, _ptr(r), K, _ptr(ids.contiguous()), H0, W0,
+                                                         _ptr(counts), _stream_ptr(M))
+    if rc == _lib.ERR_NOT_IMPLEMENTED:
+        return None
+    _lib.check(rc, "video_panoptic_counts")
+    return counts
+
+
+def video_panoptic_paint(M, padded, crop, rows, ids, lut, out_size):
+    """int32 [V, H0, W0] = lut[k] where ids_o == k and p_k >= 0.5 (as video_panoptic_counts), else 0 (inference_video_vps.py:371-386).
+    None when not covered."""
+    b = _video_out_args("video_panoptic_paint", M, padded, crop, rows, ids, out_size)
+    if b is None or int(lut.numel()) != int(rows.numel()):
+        return None
+    (M, Q, V, h, w, Hp, Wp, hi, wi), r, K, H0, W0 = b
+    lt = lut.to(device=M.device, dtype=torch.int32).contiguous()
+    out = torch.empty((V, H0, W0), dtype=torch.int32, device=M.device)
+    with _on(M):
+        rc = _lib.load().univs_video_panoptic_paint_i32(_ptr(M), Q, V, h, w, Hp, Wp, hi, wi, _ptr(r), K, _ptr(ids.contiguous()), _ptr(lt),
+                                                        H0, W0, _ptr(out), _stream_ptr(M))
+    if rc == _lib.ERR_NOT_IMPLEMENTED:
+        return None
+    _lib.check(rc, "video_panoptic_paint")
+    return out

@@ -207,3 +207,72 @@ def image_blob_logits(seed, Q, h, w, C, crop_lowres=None):
     peak = rs.randint(0, max(1, C // 3), size=Q) * 3 % C
     cls[np.arange(Q), peak] += rs.uniform(3.0, 7.0, size=Q)
     return torch.from_numpy(L.astype(np.float32)), torch.from_numpy(cls.astype(np.float32))
+
+
+class MinVISClipHead:
+    """Seeded closed-form stand-in for `sem_seg_head(features, targets=targets)` of the MinVIS-style clip loops: reads the clip's frames
+    from targets[0]["frame_indices"] and returns {"pred_logits" [1, Q, C_all], "pred_masks" [1, Q, T, h, w], "pred_embds" [1, Q, T, E],
+    "aux_outputs": []} (numpy's RandomState, so every machine makes the same values).
+
+    `n_obj` objects move through the video, each alive in a span of frames (objects enter and leave), with one class, one embedding and
+    a Gaussian blob per frame.  Per clip the query order is shuffled (the matching has to undo it), queries of dead objects report a
+    faint blob, and in every other clip one object is reported by two queries (its rows repeat in the VIS top-k).  `Q` queries of
+    which the first `Q - extra` are learnable; the last `extra` (prompt / text queries) only count in the first clip's top-k.
+    `classes`: the class of each object (indices into the dataset's slice [start, start + C) of the C_all columns)."""
+
+    def __init__(self, seed, V, Q, h, w, C_all, start, C, n_obj, extra=0, classes=None, E=32):
+        rs = np.random.RandomState(seed)
+        self.V, self.Q, self.h, self.w, self.C_all, self.start, self.C = V, Q, h, w, C_all, start, C
+        self.n_obj, self.extra, self.E = n_obj, extra, E
+        self.seed = seed
+        self.cls = np.asarray(classes if classes is not None else rs.randint(0, C, size=n_obj))
+        self.emb = rs.normal(0, 1, size=(n_obj, E))
+        self.life = []
+        for j in range(n_obj):
+            f0 = int(rs.randint(0, max(1, V // 3))) if j % 3 == 1 else 0
+            f1 = int(rs.randint(2 * V // 3, V)) if j % 3 == 2 else V - 1
+            self.life.append((f0, f1))
+        self.c0 = rs.uniform(0.2, 0.8, size=(n_obj, 2)) * (h, w)
+        self.vel = rs.uniform(-0.6, 0.6, size=(n_obj, 2))
+        self.size = rs.uniform(1.5, 4.0, size=n_obj)
+        self.peak = rs.uniform(3.0, 7.0, size=n_obj)
+        self.bg_emb = rs.normal(0, 1, size=(Q, E))
+
+    def blob(self, j, f, rs):
+        yy, xx = np.mgrid[0:self.h, 0:self.w].astype(np.float64)
+        cy, cx = self.c0[j] + self.vel[j] * f
+        alive = self.life[j][0] <= f <= self.life[j][1]
+        amp = (8.0 + self.peak[j]) if alive else 2.0
+        s = self.size[j]
+        return -5.0 + amp * np.exp(-((yy - cy) ** 2 + (xx - cx) ** 2) / (2 * s * s)) + rs.normal(0, 0.05, size=(self.h, self.w))
+
+    def __call__(self, features, targets=None):
+        frames = [int(v) for v in targets[0]["frame_indices"]]
+        i = frames[0]
+        T = len(frames)
+        rs = np.random.RandomState(self.seed * 1000 + i)
+        Ql = self.Q - self.extra
+        # query slot -> object (or -1: background); one object twice in every other clip
+        slots = list(range(self.n_obj)) + [-1] * (Ql - self.n_obj)
+        if i % 2 == 1 and Ql > self.n_obj:
+            slots[self.n_obj] = int(rs.randint(0, self.n_obj))
+        slots = list(rs.permutation(slots)) + [int(rs.randint(0, self.n_obj)) for _ in range(self.extra)]
+        masks = np.empty((self.Q, T, self.h, self.w))
+        logits = rs.normal(-4.0, 1.0, size=(self.Q, self.C_all))
+        embds = np.empty((self.Q, T, self.E))
+        for q, j in enumerate(slots):
+            for t, f in enumerate(frames):
+                if j >= 0:
+                    masks[q, t] = self.blob(j, f, rs)
+                    embds[q, t] = self.emb[j] + rs.normal(0, 0.1, size=self.E)
+                else:
+                    masks[q, t] = -6.0 + rs.normal(0, 0.5, size=(self.h, self.w))
+                    embds[q, t] = self.bg_emb[q] + rs.normal(0, 0.3, size=self.E)
+            if j >= 0:
+                alive = any(self.life[j][0] <= f <= self.life[j][1] for f in frames)
+                logits[q, self.start:self.start + self.C] = rs.normal(-3.0, 1.0, size=self.C)
+                logits[q, self.start + self.cls[j]] = rs.uniform(1.0, 4.0) if alive else rs.uniform(-2.0, 0.0)
+            else:
+                logits[q, self.start:self.start + self.C] = rs.normal(-3.5, 1.0, size=self.C)
+        f32 = lambda a: torch.from_numpy(a.astype(np.float32))[None]
+        return {"pred_logits": f32(logits), "pred_masks": f32(masks), "pred_embds": f32(embds), "aux_outputs": []}
