@@ -31,6 +31,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from .. import ops
 from ..registry import configurable
 from ..utils.comm import convert_mask_to_box
 from .results import rle_encode_masks
@@ -127,6 +128,11 @@ def panoptic_segments(counts, classes, thing_ids, overlap_threshold):
     return lut, segments_info
 
 
+def fused_or_aten(r, aten, *args):
+    """The result `r` of a fused step (ops.image_* / ops.video_*), or `aten(*args)` where its kernel does not cover the call (None)."""
+    return aten(*args) if r is None else r
+
+
 def nearest_source_index(dst, in_size: int, out_size: int):
     """ATen's nearest source index (UpSampleNearest2d.cu): min(floor(dst * (in / out)), in - 1), the scale and the product in fp32."""
     scale = np.float32(in_size) / np.float32(out_size)
@@ -206,34 +212,25 @@ class FusedSteps:
         self.aten = AtenSteps(self.L, padded, crop)
 
     def mask_stats(self):
-        from .. import ops
-        r = ops.image_mask_stats(self.L, self.padded, self.crop)
-        return self.aten.mask_stats() if r is None else r
+        return fused_or_aten(ops.image_mask_stats(self.L, self.padded, self.crop), self.aten.mask_stats)
 
     def panoptic_ids(self, planes, scores):
-        from .. import ops
-        r = ops.image_panoptic_ids(self.L, self.padded, self.crop, planes, scores)
-        return self.aten.panoptic_ids(planes, scores) if r is None else r
+        return fused_or_aten(ops.image_panoptic_ids(self.L, self.padded, self.crop, planes, scores), self.aten.panoptic_ids, planes, scores)
 
     def panoptic_paint(self, ids, lut, out_size):
-        from .. import ops
         r = ops.image_panoptic_paint(ids, torch.as_tensor(lut, dtype=torch.int32, device=ids.device), out_size)
-        return AtenSteps.panoptic_paint(ids, lut, out_size) if r is None else r
+        return fused_or_aten(r, AtenSteps.panoptic_paint, ids, lut, out_size)
 
     def semseg(self, planes, probs):
-        from .. import ops
-        r = ops.image_semseg(self.L, self.padded, self.crop, planes, probs)
-        return self.aten.semseg(planes, probs) if r is None else r
+        return fused_or_aten(ops.image_semseg(self.L, self.padded, self.crop, planes, probs), self.aten.semseg, planes, probs)
 
     def instance_masks(self, planes, out_size):
-        from .. import ops
         r = ops.image_instance_masks(self.L, self.padded, self.crop, planes, out_size)
-        return self.aten.instance_masks(planes, out_size) if r is None else r
+        return fused_or_aten(r, self.aten.instance_masks, planes, out_size)
 
 
 def _resize_bilinear(x, size):
     if x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled():
-        from .. import ops
         return ops.bilinear_resample(x, size)
     return F.interpolate(x[None], size=tuple(size), mode="bilinear", align_corners=False)[0]
 
@@ -359,7 +356,6 @@ class InferenceImageGenericSegmentation(nn.Module):
         sizes = [tuple(int(v) for v in f.shape[-2:]) for f in frames]
         Hp, Wp = self.padded_size(sizes)
         if frames[0].is_cuda and frames[0].dtype == torch.float32 and all(f.shape == frames[0].shape for f in frames):
-            from .. import ops
             out = ops.normalize_pad(torch.stack(frames), self.pixel_mean, self.pixel_std, pad_to=(Hp, Wp))
             if out is not None:
                 return ImageList(out, sizes)

@@ -41,19 +41,16 @@ import torch.nn.functional as F
 from scipy.optimize import linear_sum_assignment
 from torch import nn
 
+from .. import ops
 from ..registry import configurable
+from ..utils.comm import calculate_mask_quality_scores
 from .comm import match_from_learnable_embds
-from .image_generic_seg import InferenceImageGenericSegmentation, panoptic_segments
+from .image_generic_seg import InferenceImageGenericSegmentation, fused_or_aten, panoptic_segments
 from .results import rle_encode_masks
 from .video_entity import COMBINED_DATASETS_CATEGORY_INFO
 
 FIRST_CLIP_MAX_QUERIES = 100   # the first clip keeps the top min(Q, 100) of all queries (vis_fast :246, vps :233)
 VPS_QUALITY_STEP = 5           # calculate_mask_quality_scores(cur_masks[:, ::5]) (vps :346)
-
-
-def calculate_mask_quality_scores(mask_pred, threshold=1):
-    """univs/utils/comm.py:86-89: |m > t| / max(1, |m > -t|) per row."""
-    return (mask_pred > threshold).flatten(1).sum(-1) / (mask_pred > -threshold).flatten(1).sum(-1).clamp(min=1)
 
 
 def match_from_embds(tgt_embds, cur_embds):
@@ -124,7 +121,6 @@ def run_minvis_loop(model, images, targets, *, num_frames, window, num_queries, 
         if S is None:
             S = torch.zeros((int(perm.numel()), V) + tuple(masks.shape[-2:]), dtype=torch.float32, device=masks.device)
         if use_kernel:
-            from .. import ops
             ops.minvis_accumulate(S, masks.float(), perm, i)
         else:
             S[:, i:i + T] += masks[perm].float()
@@ -197,29 +193,22 @@ class FusedSteps:
         self.aten = AtenSteps(self.M, padded, crop)
 
     def mask_stats(self, rows, step):
-        from .. import ops
-        r = ops.video_mask_stats(self.M, self.padded, self.crop, rows, step)
-        return self.aten.mask_stats(rows, step) if r is None else r
+        return fused_or_aten(ops.video_mask_stats(self.M, self.padded, self.crop, rows, step), self.aten.mask_stats, rows, step)
 
     def instance_masks(self, rows, out_size):
-        from .. import ops
         r = ops.video_instance_masks(self.M, self.padded, self.crop, rows, out_size)
-        return self.aten.instance_masks(rows, out_size) if r is None else r
+        return fused_or_aten(r, self.aten.instance_masks, rows, out_size)
 
     def panoptic_ids(self, rows, scores):
-        from .. import ops
-        r = ops.video_panoptic_ids(self.M, self.padded, self.crop, rows, scores)
-        return self.aten.panoptic_ids(rows, scores) if r is None else r
+        return fused_or_aten(ops.video_panoptic_ids(self.M, self.padded, self.crop, rows, scores), self.aten.panoptic_ids, rows, scores)
 
     def panoptic_counts(self, rows, ids, out_size):
-        from .. import ops
         r = ops.video_panoptic_counts(self.M, self.padded, self.crop, rows, ids, out_size)
-        return self.aten.panoptic_counts(rows, ids, out_size) if r is None else r
+        return fused_or_aten(r, self.aten.panoptic_counts, rows, ids, out_size)
 
     def panoptic_paint(self, rows, ids, lut, out_size):
-        from .. import ops
         r = ops.video_panoptic_paint(self.M, self.padded, self.crop, rows, ids, torch.as_tensor(lut, dtype=torch.int32), out_size)
-        return self.aten.panoptic_paint(rows, ids, lut, out_size) if r is None else r
+        return fused_or_aten(r, self.aten.panoptic_paint, rows, ids, lut, out_size)
 
 
 def _masks_to_host(steps, rows, out_size):

@@ -1343,6 +1343,20 @@ def prompt_point_pe(xy, z, dim_t, dim_tz, scale, n):
     return out
 
 
+# ---- mask post-processing (csrc/mask_post.h: mask_stats.hip, image_post.hip, video_post.hip) -------------------------------------------
+def _post_call(name, fn, anchor, *args, uncovered=None):
+    """The epilogue of the mask_stats / image_* / minvis_accumulate / video_* wrappers: `fn(*args, stream)`, fn a function of the library
+    (`_lib.load().univs_...`, looked up by the wrapper at call time), on `anchor`'s device and stream.  True when it ran; False where
+    the kernel does not cover the call (ERR_NOT_IMPLEMENTED: the wrapper returns None and its caller keeps the ATen formulation)
+    unless `uncovered="raise"`; any other code raises under the wrapper's `name`."""
+    with _on(anchor):
+        rc = fn(*args, _stream_ptr(anchor))
+    if rc == _lib.ERR_NOT_IMPLEMENTED and uncovered != "raise":
+        return False
+    _lib.check(rc, name)
+    return True
+
+
 def mask_stats(x, t_hi=1.0, t_lo=-1.0, t_box=0.0, valid=None):
     """Per-plane statistics of mask logits in one pass (include/univs_hip.h: univs_mask_stats_f32 / _strided_f32; csrc/mask_stats.hip): x
     [..., H, W] float32 on the GPU -> int32 [..., 8] = (|{x > t_hi}|, |{x > t_lo}|, left, top, right, bottom of {x > t_box} -- inclusive,
@@ -1369,14 +1383,32 @@ def mask_stats(x, t_hi=1.0, t_lo=-1.0, t_box=0.0, valid=None):
     out = torch.empty(tuple(x.shape[:-2]) + (8,), dtype=torch.int32, device=x.device)
     if planes == 0:
         return out
-    with _on(x):
-        rc = _lib.load().univs_mask_stats_strided_f32(_ptr(x), outer, inner, so, si, H, W, hv, wv, float(t_hi), float(t_lo), float(t_box),
-                                                      _ptr(out), _stream_ptr(x))
-    if rc == _lib.ERR_NOT_IMPLEMENTED:
-        return None
-    _lib.check(rc, "mask_stats")
-    return out
+    ok = _post_call("mask_stats", _lib.load().univs_mask_stats_strided_f32, x, _ptr(x), outer, inner, so, si, H, W, hv, wv, float(t_hi),
+                    float(t_lo), float(t_box), _ptr(out))
+    return out if ok else None
 
+
+def _lowres_args(name, X, padded, crop):
+    """The prologue of the image_* (X = L [Q', h, w]) and video_* (X = M [Q', V, h, w]) wrappers; the family is the prefix of `name`.
+    Raises for the CPU, another dtype or rank, or a bad geometry; None where no kernel covers the call (2^31 limits, autograd); else
+    (X contiguous, Q, [V,] h, w, Hp, Wp, hi, wi)."""
+    video = name.startswith("video_")
+    if not X.is_cuda:
+        raise RuntimeError(f"{name}: Not implemented on the CPU (tensor on {X.device}); the HIP extension is the only implementation")
+    if X.dtype != torch.float32 or X.dim() != (4 if video else 3):
+        raise RuntimeError(f"{name}: float32 " + ("[Q, V, h, w] mask logits only" if video else "[Q, h, w] logits only"))
+    Hp, Wp = int(padded[0]), int(padded[1])
+    hi, wi = int(crop[0]), int(crop[1])
+    dims = [int(v) for v in X.shape]
+    if not (0 < hi <= Hp and 0 < wi <= Wp) or 0 in dims:
+        raise RuntimeError(f"{name}: bad geometry {'M' if video else 'L'} {tuple(X.shape)} padded {(Hp, Wp)} crop {(hi, wi)}")
+    if Hp * Wp >= 2 ** 31 or (video and dims[1] * hi * wi >= 2 ** 31) or needs_grad(X):
+        return None
+    return (X.contiguous(), *dims, Hp, Wp, hi, wi)
+
+
+def _planes_i32(planes, device):
+    return planes.to(device=device, dtype=torch.int32).contiguous()
 
 
 # ---- per-image post-processing (include/univs_hip.h: univs_image_*; csrc/image_post.hip) ----------------------------------------------
@@ -1387,62 +1419,35 @@ IMAGE_MAX_KEPT = 4096          # UNIVS_IMAGE_MAX_KEPT
 IMAGE_COVERED = 1 << 30        # UNIVS_IMAGE_COVERED: the covered bit of a panoptic id word
 
 
-def _image_args(name, L, padded, crop):
-    if not L.is_cuda:
-        raise RuntimeError(f"{name}: Not implemented on the CPU (tensor on {L.device}); the HIP extension is the only implementation")
-    if L.dtype != torch.float32 or L.dim() != 3:
-        raise RuntimeError(f"{name}: float32 [Q, h, w] logits only")
-    Hp, Wp = int(padded[0]), int(padded[1])
-    hi, wi = int(crop[0]), int(crop[1])
-    Q, h, w = (int(v) for v in L.shape)
-    if not (0 < hi <= Hp and 0 < wi <= Wp) or Q == 0 or h * w == 0:
-        raise RuntimeError(f"{name}: bad geometry L {tuple(L.shape)} padded {(Hp, Wp)} crop {(hi, wi)}")
-    if Hp * Wp >= 2 ** 31 or needs_grad(L):
-        return None
-    return L.contiguous(), Q, h, w, Hp, Wp, hi, wi
-
-
-def _planes_i32(planes, device):
-    return planes.to(device=device, dtype=torch.int32).contiguous()
-
-
 def image_mask_stats(L, padded, crop):
     """int32 [Q', 8]: the `mask_stats` record of U = bilinear(L -> padded): (|U > 1|, |U > -1|) over the whole padded plane, the box of
     {U > 0} over the crop (inclusive corners, zeros when empty), non-empty, 0 -- `calculate_mask_quality_scores` before the crop and
     `convert_mask_to_box(crop(U) > 0)` (inference_image_generic_seg.py:243, :363).  None when not covered (Q' > 65 535)."""
-    a = _image_args("image_mask_stats", L, padded, crop)
+    a = _lowres_args("image_mask_stats", L, padded, crop)
     if a is None or a[1] > 65535:
         return None
-    L, Q, h, w, Hp, Wp, hi, wi = a
+    L, Q = a[:2]
     out = torch.empty((Q, 8), dtype=torch.int32, device=L.device)
-    with _on(L):
-        rc = _lib.load().univs_image_mask_stats_f32(_ptr(L), Q, h, w, Hp, Wp, hi, wi, _ptr(out), _stream_ptr(L))
-    if rc == _lib.ERR_NOT_IMPLEMENTED:
-        return None
-    _lib.check(rc, "image_mask_stats")
-    return out
+    ok = _post_call("image_mask_stats", _lib.load().univs_image_mask_stats_f32, L, _ptr(L), *a[1:], _ptr(out))
+    return out if ok else None
 
 
 def image_panoptic_ids(L, padded, crop, planes, scores):
     """Over the crop: ids int32 [hi, wi] = k | (IMAGE_COVERED if sigmoid(U_k) >= 0.5), k the FIRST maximum over the K kept planes of
     scores[k] * sigmoid(U_{planes[k]}) (`argmax(0)`); counts int32 [K, 3] = (|ids == k|, |sigmoid(U_k) >= 0.5|, |ids == k, covered|)
     (panoptic_inference, :318-353).  None when not covered (K > IMAGE_MAX_KEPT)."""
-    a = _image_args("image_panoptic_ids", L, padded, crop)
+    a = _lowres_args("image_panoptic_ids", L, padded, crop)
     K = int(planes.numel())
     if a is None or K == 0 or K > IMAGE_MAX_KEPT or int(scores.numel()) != K:
         return None
-    L, Q, h, w, Hp, Wp, hi, wi = a
+    L, (hi, wi) = a[0], a[-2:]
     pl = _planes_i32(planes, L.device)
     sc = scores.to(device=L.device, dtype=torch.float32).contiguous()
     ids = torch.empty((hi, wi), dtype=torch.int32, device=L.device)
     counts = torch.zeros((K, 3), dtype=torch.int32, device=L.device)
-    with _on(L):
-        rc = _lib.load().univs_image_panoptic_ids_f32(_ptr(L), Q, h, w, Hp, Wp, hi, wi, _ptr(pl), _ptr(sc), K, _ptr(ids), _ptr(counts),
-                                                      _stream_ptr(L))
-    if rc == _lib.ERR_NOT_IMPLEMENTED:
-        return None
-    _lib.check(rc, "image_panoptic_ids")
-    return ids, counts
+    ok = _post_call("image_panoptic_ids", _lib.load().univs_image_panoptic_ids_f32, L, _ptr(L), *a[1:], _ptr(pl), _ptr(sc), K, _ptr(ids),
+                    _ptr(counts))
+    return (ids, counts) if ok else None
 
 
 def image_panoptic_paint(ids, lut, out_size):
@@ -1461,58 +1466,48 @@ def image_panoptic_paint(ids, lut, out_size):
     lt = lut.to(device=ids.device, dtype=torch.int32).contiguous()
     out = torch.empty((H0, W0), dtype=torch.int32, device=ids.device)
     seen = torch.zeros(K, dtype=torch.int32, device=ids.device)
-    with _on(ids):
-        rc = _lib.load().univs_image_panoptic_paint_i32(_ptr(ids), hi, wi, _ptr(lt), K, H0, W0, _ptr(out), _ptr(seen), _stream_ptr(ids))
-    if rc == _lib.ERR_NOT_IMPLEMENTED:
-        return None
-    _lib.check(rc, "image_panoptic_paint")
-    return out, seen
+    ok = _post_call("image_panoptic_paint", _lib.load().univs_image_panoptic_paint_i32, ids, _ptr(ids), hi, wi, _ptr(lt), K, H0, W0,
+                    _ptr(out), _ptr(seen))
+    return (out, seen) if ok else None
 
 
 def image_semseg(L, padded, crop, planes, probs):
     """float32 [C, hi, wi] = einsum("qc,qhw->chw", probs, sigmoid(crop(U_planes))) (semantic_inference, :296-300) with the sigmoid planes
     made per tile and never stored; queries summed in ascending order, one fp32 rounding per term.  None when not covered."""
-    a = _image_args("image_semseg", L, padded, crop)
+    a = _lowres_args("image_semseg", L, padded, crop)
     if a is None or needs_grad(probs) or probs.dim() != 2 or int(probs.shape[0]) != int(planes.numel()):
         return None
-    L, Q, h, w, Hp, Wp, hi, wi = a
+    L, (hi, wi) = a[0], a[-2:]
     Qs, C = int(probs.shape[0]), int(probs.shape[1])
     if C == 0 or (C + 159) // 160 > 65535:
         return None
     pl = _planes_i32(planes, L.device)
     P = probs.to(device=L.device, dtype=torch.float32).contiguous()
     out = torch.empty((C, hi, wi), dtype=torch.float32, device=L.device)
-    with _on(L):
-        rc = _lib.load().univs_image_semseg_f32(_ptr(L), Q, h, w, Hp, Wp, hi, wi, _ptr(pl) if Qs else None, _ptr(P) if Qs else None, Qs, C,
-                                                _ptr(out), _stream_ptr(L))
-    if rc == _lib.ERR_NOT_IMPLEMENTED:
-        return None
-    _lib.check(rc, "image_semseg")
-    return out
+    ok = _post_call("image_semseg", _lib.load().univs_image_semseg_f32, L, _ptr(L), *a[1:], _ptr(pl) if Qs else None,
+                    _ptr(P) if Qs else None, Qs, C, _ptr(out))
+    return out if ok else None
 
 
 def image_instance_masks(L, padded, crop, planes, out_size):
     """uint8 [N, H0, W0] = bilinear(crop(U_planes) -> out_size) > 0 (instance_inference's second resize and binarisation, :414-422; both
     resizes as ATen's) and int32 [N, 8] records of their boxes (left, top, right, bottom at [2:6], zeros when empty; :420).  None when not
     covered (N > 65 535)."""
-    a = _image_args("image_instance_masks", L, padded, crop)
+    a = _lowres_args("image_instance_masks", L, padded, crop)
     N = int(planes.numel())
     H0, W0 = int(out_size[0]), int(out_size[1])
     if a is None or N > 65535 or H0 < 1 or W0 < 1 or H0 * W0 >= 2 ** 31:
         return None
-    L, Q, h, w, Hp, Wp, hi, wi = a
+    L = a[0]
     pl = _planes_i32(planes, L.device)
     masks = torch.empty((N, H0, W0), dtype=torch.uint8, device=L.device)
     boxes = torch.zeros((N, 8), dtype=torch.int32, device=L.device)
     if N == 0:
         return masks, boxes
-    with _on(L):
-        rc = _lib.load().univs_image_instance_masks_u8(_ptr(L), Q, h, w, Hp, Wp, hi, wi, _ptr(pl), N, H0, W0, _ptr(masks), _ptr(boxes),
-                                                       _stream_ptr(L))
-    if rc == _lib.ERR_NOT_IMPLEMENTED:
-        return None
-    _lib.check(rc, "image_instance_masks")
-    return masks, boxes
+    ok = _post_call("image_instance_masks", _lib.load().univs_image_instance_masks_u8, L, _ptr(L), *a[1:], _ptr(pl), N, H0, W0, _ptr(masks),
+                    _ptr(boxes))
+    return (masks, boxes) if ok else None
+
 
 def token_mean(x, add=None):
     """Mean over the non-blank tokens (univs_token_mean_f32): x [n, L, T, C] -> [n, T, C] = x.sum(1) / max(1, number of tokens l whose
@@ -1741,57 +1736,37 @@ def minvis_accumulate(S, M, perm, i):
         raise RuntimeError(f"minvis_accumulate: S {tuple(S.shape)}, M {tuple(M.shape)}, perm {int(perm.numel())}, i {i}")
     M = M.contiguous()
     pm = _planes_i32(perm, S.device)
-    with _on(S):
-        rc = _lib.load().univs_minvis_accumulate_f32(_ptr(S), Q, V, h, w, _ptr(M), Qm, T, _ptr(pm), int(i), _stream_ptr(S))
-    _lib.check(rc, "minvis_accumulate")
+    _post_call("minvis_accumulate", _lib.load().univs_minvis_accumulate_f32, S, _ptr(S), Q, V, h, w, _ptr(M), Qm, T, _ptr(pm), int(i),
+               uncovered="raise")
     return S
-
-
-def _video_args(name, M, padded, crop):
-    if not M.is_cuda:
-        raise RuntimeError(f"{name}: Not implemented on the CPU (tensor on {M.device}); the HIP extension is the only implementation")
-    if M.dtype != torch.float32 or M.dim() != 4:
-        raise RuntimeError(f"{name}: float32 [Q, V, h, w] mask logits only")
-    Hp, Wp = int(padded[0]), int(padded[1])
-    hi, wi = int(crop[0]), int(crop[1])
-    Q, V, h, w = (int(v) for v in M.shape)
-    if not (0 < hi <= Hp and 0 < wi <= Wp) or Q * V == 0 or h * w == 0:
-        raise RuntimeError(f"{name}: bad geometry M {tuple(M.shape)} padded {(Hp, Wp)} crop {(hi, wi)}")
-    if Hp * Wp >= 2 ** 31 or V * hi * wi >= 2 ** 31 or needs_grad(M):
-        return None
-    return M.contiguous(), Q, V, h, w, Hp, Wp, hi, wi
 
 
 def video_mask_stats(M, padded, crop, rows, step):
     """int32 [K, 2] = (|U > 1|, |U > -1|) of rows[k] over the crop of frames 0, step, 2 step, ... (calculate_mask_quality_scores(
     mask_pred[:, ::step]) after the resize and crop: inference_video_vis_fast.py:326-328, inference_video_vps.py:346-347).  None when not
     covered."""
-    a = _video_args("video_mask_stats", M, padded, crop)
+    a = _lowres_args("video_mask_stats", M, padded, crop)
     K = int(rows.numel())
     if a is None or K > 65535 or int(step) < 1:
         return None
-    M, Q, V, h, w, Hp, Wp, hi, wi = a
+    M = a[0]
     counts = torch.zeros((K, 2), dtype=torch.int32, device=M.device)
     if K == 0:
         return counts
     r = _planes_i32(rows, M.device)
-    with _on(M):
-        rc = _lib.load().univs_video_mask_stats_f32(_ptr(M), Q, V, h, w, Hp, Wp, hi, wi, _ptr(r), K, int(step), _ptr(counts), _stream_ptr(M))
-    if rc == _lib.ERR_NOT_IMPLEMENTED:
-        return None
-    _lib.check(rc, "video_mask_stats")
-    return counts
+    ok = _post_call("video_mask_stats", _lib.load().univs_video_mask_stats_f32, M, _ptr(M), *a[1:], _ptr(r), K, int(step), _ptr(counts))
+    return counts if ok else None
 
 
 def video_instance_masks(M, padded, crop, rows, out_size, out=None):
     """uint8 [N, V, H0, W0] = bilinear(crop(U_{rows[i], v}) -> out_size) > 0 (inference_video_vis_fast.py:330-339; both resizes as ATen's).
     `out`: an optional uint8 tensor of that shape to write into.  None when not covered (N V > 65 535)."""
-    a = _video_args("video_instance_masks", M, padded, crop)
+    a = _lowres_args("video_instance_masks", M, padded, crop)
     N = int(rows.numel())
     H0, W0 = int(out_size[0]), int(out_size[1])
     if a is None or H0 < 1 or W0 < 1 or H0 * W0 >= 2 ** 31:
         return None
-    M, Q, V, h, w, Hp, Wp, hi, wi = a
+    M, V = a[0], a[2]
     if N * V > 65535:
         return None
     masks = torch.empty((N, V, H0, W0), dtype=torch.uint8, device=M.device) if out is None else out
@@ -1800,35 +1775,27 @@ def video_instance_masks(M, padded, crop, rows, out_size, out=None):
     if N == 0:
         return masks
     r = _planes_i32(rows, M.device)
-    with _on(M):
-        rc = _lib.load().univs_video_instance_masks_u8(_ptr(M), Q, V, h, w, Hp, Wp, hi, wi, _ptr(r), N, H0, W0, _ptr(masks), _stream_ptr(M))
-    if rc == _lib.ERR_NOT_IMPLEMENTED:
-        return None
-    _lib.check(rc, "video_instance_masks")
-    return masks
+    ok = _post_call("video_instance_masks", _lib.load().univs_video_instance_masks_u8, M, _ptr(M), *a[1:], _ptr(r), N, H0, W0, _ptr(masks))
+    return masks if ok else None
 
 
 def video_panoptic_ids(M, padded, crop, rows, scores):
     """int32 [V, hi, wi] over the crop: the FIRST k maximising scores[k] * sigmoid(U_{rows[k]}), -1 where sigmoid(U_k) < 0.5 for every k
     (inference_video_vps.py:348-353).  None when not covered."""
-    a = _video_args("video_panoptic_ids", M, padded, crop)
+    a = _lowres_args("video_panoptic_ids", M, padded, crop)
     K = int(rows.numel())
     if a is None or K == 0 or int(scores.numel()) != K:
         return None
-    M, Q, V, h, w, Hp, Wp, hi, wi = a
+    M, V, (hi, wi) = a[0], a[2], a[-2:]
     r = _planes_i32(rows, M.device)
     sc = scores.to(device=M.device, dtype=torch.float32).contiguous()
     ids = torch.empty((V, hi, wi), dtype=torch.int32, device=M.device)
-    with _on(M):
-        rc = _lib.load().univs_video_panoptic_ids_i32(_ptr(M), Q, V, h, w, Hp, Wp, hi, wi, _ptr(r), _ptr(sc), K, _ptr(ids), _stream_ptr(M))
-    if rc == _lib.ERR_NOT_IMPLEMENTED:
-        return None
-    _lib.check(rc, "video_panoptic_ids")
-    return ids
+    ok = _post_call("video_panoptic_ids", _lib.load().univs_video_panoptic_ids_i32, M, _ptr(M), *a[1:], _ptr(r), _ptr(sc), K, _ptr(ids))
+    return ids if ok else None
 
 
 def _video_out_args(name, M, padded, crop, rows, ids, out_size):
-    a = _video_args(name, M, padded, crop)
+    a = _lowres_args(name, M, padded, crop)
     K = int(rows.numel())
     H0, W0 = int(out_size[0]), int(out_size[1])
     if a is None or K == 0 or K > IMAGE_MAX_KEPT or H0 < 1 or W0 < 1 or a[2] * H0 * W0 >= 2 ** 31:
@@ -1844,15 +1811,12 @@ def video_panoptic_counts(M, padded, crop, rows, ids, out_size):
     b = _video_out_args("video_panoptic_counts", M, padded, crop, rows, ids, out_size)
     if b is None:
         return None
-    (M, Q, V, h, w, Hp, Wp, hi, wi), r, K, H0, W0 = b
+    a, r, K, H0, W0 = b
+    M = a[0]
     counts = torch.zeros((K, 3), dtype=torch.int32, device=M.device)
-    with _on(M):
-        rc = _lib.load().univs_video_panoptic_counts_i32(_ptr(M), Q, V, h, w, Hp, Wp, hi, wi, _ptr(r), K, _ptr(ids.contiguous()), H0, W0,
-                                                         _ptr(counts), _stream_ptr(M))
-    if rc == _lib.ERR_NOT_IMPLEMENTED:
-        return None
-    _lib.check(rc, "video_panoptic_counts")
-    return counts
+    ok = _post_call("video_panoptic_counts", _lib.load().univs_video_panoptic_counts_i32, M, _ptr(M), *a[1:], _ptr(r), K,
+                    _ptr(ids.contiguous()), H0, W0, _ptr(counts))
+    return counts if ok else None
 
 
 def video_panoptic_paint(M, padded, crop, rows, ids, lut, out_size):
@@ -1861,13 +1825,10 @@ def video_panoptic_paint(M, padded, crop, rows, ids, lut, out_size):
     b = _video_out_args("video_panoptic_paint", M, padded, crop, rows, ids, out_size)
     if b is None or int(lut.numel()) != int(rows.numel()):
         return None
-    (M, Q, V, h, w, Hp, Wp, hi, wi), r, K, H0, W0 = b
+    a, r, K, H0, W0 = b
+    M, V = a[0], a[2]
     lt = lut.to(device=M.device, dtype=torch.int32).contiguous()
     out = torch.empty((V, H0, W0), dtype=torch.int32, device=M.device)
-    with _on(M):
-        rc = _lib.load().univs_video_panoptic_paint_i32(_ptr(M), Q, V, h, w, Hp, Wp, hi, wi, _ptr(r), K, _ptr(ids.contiguous()), _ptr(lt),
-                                                        H0, W0, _ptr(out), _stream_ptr(M))
-    if rc == _lib.ERR_NOT_IMPLEMENTED:
-        return None
-    _lib.check(rc, "video_panoptic_paint")
-    return out
+    ok = _post_call("video_panoptic_paint", _lib.load().univs_video_panoptic_paint_i32, M, _ptr(M), *a[1:], _ptr(r), K,
+                    _ptr(ids.contiguous()), _ptr(lt), H0, W0, _ptr(out))
+    return out if ok else None
