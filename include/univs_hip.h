@@ -549,6 +549,26 @@ int univs_normalize_pad_f32(const float* x, const float* mean, const float* std,
 int univs_bilinear_resample_f32(const float* in, const float* addend, float* out, long long planes,
                                 int Hin, int Win, int Hout, int Wout, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Semantic extraction: bilinear up-sampling, crop and nearest compression of the mask features as one gather (semantic_extract.hip).
+ * Replaces: univs/inference/inference_video_semantic_extraction.py:219-238
+ *             mask_features = F.interpolate(mask_features, size=interim_size, mode="bilinear", align_corners=False)
+ *             mask_features = mask_features[..., :image_size[0], :image_size[1]]
+ *             compression_mask_features = F.interpolate(mask_features, size=(hc, wc), mode="nearest")
+ *           and the `[::t_itv]` applied to the clips' concatenation before it is saved (:261-262).  The up-sampled stack
+ *           [T, C, Hp, Wp] is never written:
+ *   out[k, c, oy, ox] = U[t_first + k * t_step, c, sy(oy), sx(ox)],  U = bilinear(in -> Hp x Wp) with the taps, weights and expression
+ *   order of univs_bilinear_resample_f32 (bit-identical to it), sy(oy) = min(floor(oy * (float(Hi) / hc)), Hi - 1) in fp32 (ATen's
+ *   nearest source index of the resize of the crop (Hi, Wi) -> (hc, wc)), sx alike.
+ *   in   [T, C, h, w]     contiguous
+ *   out  [K, C, hc, wc]   contiguous; may be rows of a larger [V', C, hc, wc] buffer (16-byte stores when wc % 4 == 0 and out is
+ *                         16-byte aligned)
+ * K <= 0: UNIVS_OK, nothing launched.  UNIVS_ERR_INVALID_ARGUMENT for non-positive sizes, Hi > Hp, Wi > Wp, t_first < 0, t_step < 1 or
+ * t_first + (K - 1) * t_step >= T; UNIVS_ERR_NOT_IMPLEMENTED when h * w or hc * wc reaches 2^31.
+ * ------------------------------------------------------------------------------------------- */
+int univs_bilinear_crop_nearest_f32(const float* in, int T, int C, int h, int w, int Hp, int Wp, int Hi, int Wi, int hc, int wc,
+                                    int t_first, int t_step, int K, float* out, void* stream);
+
 /* The three attention-mask resolutions of the decoder in one pass: out2 / out4 / out8 = univs_bilinear_resample_f32(in) to
  * (H/2, W/2), (H/4, W/4), (H/8, W/8) -- bit-identical to the three separate calls, the input is read once
  * (...decoder_univs.py:555-558 resizes to the sizes of the three feature levels, strides 8 / 16 / 32 against mask features

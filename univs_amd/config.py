@@ -140,7 +140,9 @@ def get_cfg():
                       VIDEO_UNIFIED_INFERENCE_QUERIES="prompt", VIDEO_UNIFIED_INFERENCE_ENTITIES="",
                       BOX_NMS_THRESH=0.75, TEMPORAL_CONSISTENCY_THRESHOLD=0.05, DETECT_NEWLY_OBJECT_THRESHOLD=0.05,
                       CUSTOM_VIDEOS_ENABLE=False, CUSTOM_VIDEOS_TEXT=[],
-                      SEMANTIC_EXTRACTION=CN(ENABLE=False), DISABLE_SEMANTIC_QUERIES=False)
+                      # univs/config.py:156-160
+                      SEMANTIC_EXTRACTION=CN(ENABLE=False, COMPRESSION_RATIO=32, COMPRESSION_RATIO_TEMPORAL=1, OUTPUT_DIR=""),
+                      DISABLE_SEMANTIC_QUERIES=False)
     c.INPUT = CN(FORMAT="RGB", SAMPLING_FRAME_NUM=2, MIN_SIZE_TEST=800, MAX_SIZE_TEST=1333,
                  LSJ_AUG=CN(ENABLED=True, SQUARE_ENABLED=True, IMAGE_SIZE=1024, MIN_SCALE=0.25, MAX_SCALE=4.0))
     c.TEST = CN(DETECTIONS_PER_IMAGE=100)

@@ -56,6 +56,7 @@ int msda_prepare_f32(const float*, int, int, const float*, long long, const Leve
 int bilinear_resample_f32(const float*, const float*, float*, long long, int, int, int, int, hipStream_t);
 int upsample2x_add_f32(const float*, const float*, const float*, float*, long long, int, int, hipStream_t);
 int normalize_pad_f32(const float*, float*, long long, int, int, int, int, int, const float*, const float*, hipStream_t);
+int bilinear_crop_nearest_f32(const float*, float*, int, int, int, int, int, int, int, int, int, int, int, int, hipStream_t);
 int conv3x3_nhwc_f16x3_f32(const float*, const void*, const float*, float*, int, int, int, int, int, hipStream_t);
 int small_chain_f32(const float*, int, const void* const*, const float* const*, const float* const*, const int*, const float*, const float*,
                     float, float*, float*, long long, int, hipStream_t);
@@ -742,6 +743,33 @@ int univs_normalize_pad_f32(const float* x, const float* mean, const float* std,
   }
   const int rc = normalize_pad_f32(x, out, T, C, H, W, Hp, Wp, mean, std, static_cast<hipStream_t>(stream));
   if (rc == UNIVS_ERR_NOT_IMPLEMENTED) set_error("univs_normalize_pad_f32: T * C = %lld planes not covered (<= 65535)", T * C);
+  return rc;
+}
+
+int univs_bilinear_crop_nearest_f32(const float* in, int T, int C, int h, int w, int Hp, int Wp, int Hi, int Wi, int hc, int wc, int t_first,
+                                    int t_step, int K, float* out, void* stream) {
+  clear_sticky_error();
+  if (T < 1 || C < 1 || h < 1 || w < 1 || Hp < 1 || Wp < 1 || Hi < 1 || Wi < 1 || hc < 1 || wc < 1 || Hi > Hp || Wi > Wp) {
+    set_error("univs_bilinear_crop_nearest_f32: bad geometry in [%d, %d, %d, %d] padded %dx%d crop %dx%d out %dx%d", T, C, h, w, Hp, Wp, Hi,
+              Wi, hc, wc);
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  if (t_first < 0 || t_step < 1) {
+    set_error("univs_bilinear_crop_nearest_f32: t_first=%d t_step=%d (t_first >= 0, t_step >= 1)", t_first, t_step);
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  if (K <= 0) return UNIVS_OK;
+  if ((long long)t_first + (long long)(K - 1) * t_step >= T) {
+    set_error("univs_bilinear_crop_nearest_f32: frames %d + k * %d, k < %d, leave the %d frames of the input", t_first, t_step, K, T);
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  if (!in || !out) {
+    set_error("univs_bilinear_crop_nearest_f32: NULL data pointer");
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  const int rc = bilinear_crop_nearest_f32(in, out, C, h, w, Hp, Wp, Hi, Wi, hc, wc, t_first, t_step, K, static_cast<hipStream_t>(stream));
+  if (rc == UNIVS_ERR_NOT_IMPLEMENTED)
+    set_error("univs_bilinear_crop_nearest_f32: not covered (h w < 2^31, hc wc < 2^31)");
   return rc;
 }
 

@@ -2,6 +2,7 @@
 back into (`model.backbone`, `model.sem_seg_head`, `model.prepare_targets`, `model.text_prompt_encoder`) and its
 `forward_inference` dispatch (:416-452):
 
+    MODEL.UniVS.TEST.SEMANTIC_EXTRACTION.ENABLE (checked first) -> InferenceVideoSemanticExtraction.eval
     image datasets ('coco*' / 'ade20k*')                        -> InferenceImageGenericSegmentation.eval
     task 'grounding' / 'sot', or custom text prompts            -> InferenceVideoVOS.eval
     category-specified tasks (ytvis / ovis / vipseg / vspw,
@@ -10,8 +11,8 @@ back into (`model.backbone`, `model.sem_seg_head`, `model.prepare_targets`, `mod
     TRACKER_TYPE 'minvis'                                        -> InferenceVideoVISFast.eval
     unified inference disabled: 'vipseg*' / 'vpsw*'              -> InferenceVideoVPS.eval (which serves 'vipseg*' only)
 
-The other branches of the reference (the MDQE tracker of the non-unified mode, EMA teacher weights, semantic-feature
-extraction, and all of training: losses, matcher, `forward` in train mode) are out of scope of the hot path and raise.
+The other branches of the reference (the MDQE tracker of the non-unified mode, EMA teacher weights, and all of training:
+losses, matcher, `forward` in train mode) are out of scope of the hot path and raise.
 """
 import torch
 from torch import nn
@@ -19,6 +20,7 @@ from torch import nn
 from ...inference.image_generic_seg import InferenceImageGenericSegmentation
 from ...inference.video_entity import InferenceVideoEntity
 from ...inference.video_minvis import InferenceVideoVISFast, InferenceVideoVPS
+from ...inference.video_semantic_extraction import InferenceVideoSemanticExtraction
 from ...inference.video_vos import InferenceVideoVOS
 from ...prepare_targets import PrepareTargets
 from ...registry import META_ARCH_REGISTRY, configurable
@@ -31,7 +33,8 @@ class UniVS_Prompt(nn.Module):
     def __init__(self, *, backbone, sem_seg_head, prepare_targets, text_prompt_encoder, inference_video_entity,
                  inference_video_vos, pixel_mean, pixel_std, video_unified_inference_enable: bool,
                  custom_videos_enable: bool, custom_videos_text, inference_img_generic_seg=None, inference_video_vis_fast=None,
-                 inference_video_vps=None, tracker_type: str = "minvis"):
+                 inference_video_vps=None, tracker_type: str = "minvis", inference_video_semantic_extraction=None,
+                 semantic_extraction_enable: bool = False):
         super().__init__()
         self.backbone = backbone
         self.sem_seg_head = sem_seg_head
@@ -43,6 +46,8 @@ class UniVS_Prompt(nn.Module):
         self.inference_video_vis_fast = inference_video_vis_fast
         self.inference_video_vps = inference_video_vps
         self.tracker_type = tracker_type
+        self.inference_video_semantic_extraction = inference_video_semantic_extraction
+        self.semantic_extraction_enable = semantic_extraction_enable
         self.register_buffer("pixel_mean", torch.tensor(pixel_mean, dtype=torch.float32).view(-1, 1, 1), False)
         self.register_buffer("pixel_std", torch.tensor(pixel_std, dtype=torch.float32).view(-1, 1, 1), False)
         self.video_unified_inference_enable = video_unified_inference_enable
@@ -75,6 +80,8 @@ class UniVS_Prompt(nn.Module):
             "inference_img_generic_seg": InferenceImageGenericSegmentation(cfg),
             "inference_video_vis_fast": InferenceVideoVISFast(cfg), "inference_video_vps": InferenceVideoVPS(cfg),
             "tracker_type": cfg.MODEL.BoxVIS.TEST.TRACKER_TYPE,
+            "inference_video_semantic_extraction": InferenceVideoSemanticExtraction(cfg),
+            "semantic_extraction_enable": test.SEMANTIC_EXTRACTION.ENABLE,
         }
 
     @property
@@ -88,6 +95,8 @@ class UniVS_Prompt(nn.Module):
 
     @torch.no_grad()
     def forward_inference(self, batched_inputs):
+        if self.semantic_extraction_enable:                                              # before everything else (univs_prompt.py:420-421)
+            return self._driver("inference_video_semantic_extraction", "semantic extraction").eval(self, batched_inputs)
         name = batched_inputs[0]["dataset_name"]
         if name.startswith("coco") or name.startswith("ade20k"):
             if self.inference_img_generic_seg is None:
@@ -114,10 +123,10 @@ class UniVS_Prompt(nn.Module):
             return self._driver("inference_video_vps").eval(self, batched_inputs)
         raise ValueError(f"Not support to eval the dataset {name} yet")
 
-    def _driver(self, attr):
+    def _driver(self, attr, what="non-unified video inference"):
         d = getattr(self, attr, None)
         if d is None:
-            raise NotImplementedError(f"non-unified video inference: this model was built without {attr}")
+            raise NotImplementedError(f"{what}: this model was built without {attr}")
         return d
 
 

@@ -877,6 +877,45 @@ def bilinear_resample(x, size, addend=None):
     return out
 
 
+def bilinear_crop_nearest(x, padded, crop, size, *, t_first=0, t_step=1, out=None):
+    """F.interpolate(F.interpolate(x, padded, mode="bilinear", align_corners=False)[..., :crop[0], :crop[1]], size, mode="nearest")
+    [t_first::t_step] for float32 x [T, C, h, w] on the GPU as one gather (include/univs_hip.h: univs_bilinear_crop_nearest_f32;
+    inference_video_semantic_extraction.py:219-238): the up-sampled [T, C, Hp, Wp] stack is never built, dropped frames are not read.
+    Bit-identical to `bilinear_resample` followed by ATen's nearest resize.  `out`: an optional contiguous float32 [K, C, hc, wc] to write
+    into, K <= the number of selected frames (rows of a larger per-video buffer: `video[a:b]`).  None where no kernel covers the shape."""
+    _inference_only("bilinear_crop_nearest", x)
+    if not x.is_cuda:
+        raise RuntimeError(f"bilinear_crop_nearest: Not implemented on the CPU (tensor on {x.device}); the HIP extension is the only "
+                           "implementation")
+    if x.dtype != torch.float32 or x.dim() != 4:
+        raise RuntimeError("bilinear_crop_nearest: float32 [T, C, h, w] only")
+    x = x.contiguous()
+    T, C, h, w = (int(v) for v in x.shape)
+    Hp, Wp, Hi, Wi, hc, wc = (int(v) for v in (*padded, *crop, *size))
+    t_first, t_step = int(t_first), int(t_step)
+    if min(C, h, w, Hp, Wp, Hi, Wi, hc, wc) < 1 or Hi > Hp or Wi > Wp or t_first < 0 or t_step < 1:
+        raise RuntimeError(f"bilinear_crop_nearest: bad geometry x {tuple(x.shape)} padded {(Hp, Wp)} crop {(Hi, Wi)} size {(hc, wc)} "
+                           f"t_first {t_first} t_step {t_step}")
+    K = len(range(t_first, T, t_step))
+    if out is None:
+        out = torch.empty((K, C, hc, wc), dtype=torch.float32, device=x.device)
+    else:
+        if (out.dtype != torch.float32 or out.device != x.device or not out.is_contiguous() or out.dim() != 4
+                or tuple(out.shape[1:]) != (C, hc, wc) or int(out.shape[0]) > K):
+            raise RuntimeError(f"bilinear_crop_nearest: out {tuple(out.shape)} {out.dtype}, expected contiguous float32 [<= {K}, {C}, {hc}, "
+                               f"{wc}] on {x.device}")
+        K = int(out.shape[0])
+    if K == 0:
+        return out
+    with _on(x):
+        rc = _lib.load().univs_bilinear_crop_nearest_f32(_ptr(x), T, C, h, w, Hp, Wp, Hi, Wi, hc, wc, t_first, t_step, K, _ptr(out),
+                                                        _stream_ptr(x))
+    if rc == _lib.ERR_NOT_IMPLEMENTED:
+        return None
+    _lib.check(rc, "bilinear_crop_nearest")
+    return out
+
+
 def normalize_pad(x, mean, std, size_divisibility=0, pad_to=None):
     """`F.pad((x - mean) / std, ...)` in one pass (include/univs_hip.h: univs_normalize_pad_f32): the pre-step of a clip
     (inference_video_entity.py:246-250).  x [T, C, H, W] float32 on the GPU, mean / std [C] (any broadcastable shape with C elements);

@@ -276,3 +276,32 @@ class MinVISClipHead:
                 logits[q, self.start:self.start + self.C] = rs.normal(-3.5, 1.0, size=self.C)
         f32 = lambda a: torch.from_numpy(a.astype(np.float32))[None]
         return {"pred_logits": f32(logits), "pred_masks": f32(masks), "pred_embds": f32(embds), "aux_outputs": []}
+
+
+class SemanticClipHead:
+    """Seeded closed-form stand-in for `sem_seg_head(features, targets=targets)` under semantic extraction
+    (inference/video_semantic_extraction.py): returns {"pred_embds" [T, C, N], "mask_features" [T, C, h, w]} as functions of
+    targets[0]["frame_indices"] only (numpy's RandomState per frame, so every machine makes the same values and a frame has the same
+    values whichever clip it falls in): smooth planes (a plane wave per channel, drifting with the frame) plus noise, so that both the
+    bilinear weights and the choice of the nearest pixel show.  `calls` records what each call received: (first_frame_idx,
+    frame_indices, the number of frames of the features handed in)."""
+
+    def __init__(self, seed, C, N, h, w):
+        self.seed, self.C, self.N, self.h, self.w = seed, C, N, h, w
+        self.calls = []
+
+    def frame(self, f):
+        rs = np.random.RandomState(self.seed * 1000 + f)
+        yy, xx = np.mgrid[0:self.h, 0:self.w].astype(np.float64)
+        ky, kx = rs.uniform(-0.8, 0.8, size=(2, self.C, 1, 1))
+        ph = rs.uniform(0, 2 * np.pi, size=(self.C, 1, 1))
+        feat = 2.0 * np.sin(ky * yy + kx * xx + ph + 0.3 * f) + rs.normal(0, 0.25, size=(self.C, self.h, self.w))
+        tok = rs.normal(0, 1, size=(self.C, self.N))
+        return tok.astype(np.float32), feat.astype(np.float32)
+
+    def __call__(self, features, targets=None):
+        frames = [int(v) for v in targets[0]["frame_indices"]]
+        handed = int(next(iter(features.values())).shape[0])
+        self.calls.append((int(targets[0]["first_frame_idx"]), frames, handed))
+        toks, feats = zip(*(self.frame(f) for f in frames))
+        return {"pred_embds": torch.from_numpy(np.stack(toks)), "mask_features": torch.from_numpy(np.stack(feats))}
