@@ -795,6 +795,19 @@ int univs_video_panoptic_counts_i32(const float* M, int Q, int V, int h, int w, 
 int univs_video_panoptic_paint_i32(const float* M, int Q, int V, int h, int w, int Hp, int Wp, int hi, int wi, const int32_t* rows, int K,
                                    const int32_t* ids, const int32_t* lut, int H0, int W0, int32_t* out, void* stream);
 
+/* ---- scoring a video panoptic result (csrc/pair_count.hip) ----------------------------------------------------------------------------
+ * counts [T, G + 1, P + 1] int32 (zeroed by the caller) += the pixels of frame t whose ground-truth id is gt_ids[g] and whose predicted id
+ * is pred_ids[p]; row G / column P collect the ids that are not in the (ascending, unique) tables.  first_unknown [T, 2] int32 (filled
+ * with -1 by the caller) = the largest unlisted id of the frame's ground truth ([t][0]) and prediction ([t][1]); it stays -1 when none is
+ * >= 0.  gt / pred: uint8 [T, H, W, 3] when *_rgb != 0 (id = R + 256 G + 65536 B, the decoded panoptic PNG), else int32 [T, H, W].
+ * G, P <= 1024 and (G + 1)(P + 1) <= 16384 (the LDS histogram), T <= 65535, both maps dword-aligned; else UNIVS_ERR_NOT_IMPLEMENTED.
+ * The maps are read in whole dwords: a uint8 map whose T H W 3 bytes are no multiple of 4 must be readable up to the next dword (up to 3
+ * bytes beyond its end; any device allocation is).
+ * Replaces: the np.unique over (gt id, pred id) keys that the reference runs once per window and metric
+ * (univs/evaluation/eval_vpq_vps.py:156-165, eval_stquality_vps.py:139-195). */
+int univs_panoptic_pair_counts(const void* gt, int gt_rgb, const void* pred, int pred_rgb, int T, int H, int W, const int32_t* gt_ids, int G,
+                               const int32_t* pred_ids, int P, int32_t* counts, int32_t* first_unknown, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -88,6 +88,7 @@ int video_panoptic_ids_i32(const float*, int, int, int, int, int, int, int, int,
 int video_panoptic_counts_i32(const float*, int, int, int, int, int, int, int, int, const int*, int, const int*, int, int, int*, hipStream_t);
 int video_panoptic_paint_i32(const float*, int, int, int, int, int, int, int, int, const int*, int, const int*, const int*, int, int, int*,
                              hipStream_t);
+int panoptic_pair_counts(const void*, int, const void*, int, int, int, int, const int*, int, const int*, int, int*, int*, hipStream_t);
 int prompt_tokens_f32(const float*, const long long*, const float*, const long long*, const float*, const float*, const long long*,
                       const uint8_t*, const uint8_t*, const float*, const long long*, int, int, int, int, int, int, int, float*, float*,
                       uint8_t*, hipStream_t);
@@ -1248,6 +1249,23 @@ int univs_video_panoptic_paint_i32(const float* M, int Q, int V, int h, int w, i
     return UNIVS_ERR_INVALID_ARGUMENT;
   }
   return video_panoptic_paint_i32(M, Q, V, h, w, Hp, Wp, hi, wi, rows, K, ids, lut, H0, W0, out, static_cast<hipStream_t>(stream));
+}
+
+int univs_panoptic_pair_counts(const void* gt, int gt_rgb, const void* pred, int pred_rgb, int T, int H, int W, const int32_t* gt_ids, int G,
+                               const int32_t* pred_ids, int P, int32_t* counts, int32_t* first_unknown, void* stream) {
+  clear_sticky_error();
+  if (T < 1 || H < 1 || W < 1 || G < 1 || P < 1 || (long long)T * H * W > (1LL << 40)) {
+    set_error("univs_panoptic_pair_counts: bad dimensions T=%d H=%d W=%d G=%d P=%d", T, H, W, G, P);
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  if (!gt || !pred || !gt_ids || !pred_ids || !counts || !first_unknown) {
+    set_error("univs_panoptic_pair_counts: NULL data pointer");
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  return not_covered("univs_panoptic_pair_counts",
+                     panoptic_pair_counts(gt, gt_rgb, pred, pred_rgb, T, H, W, gt_ids, G, pred_ids, P, counts, first_unknown,
+                                          static_cast<hipStream_t>(stream)),
+                     "G, P <= 1024, (G + 1)(P + 1) <= 16384, T <= 65535, H W < 2^31, dword-aligned maps");
 }
 
 int univs_window_attention_image_f32(const float* qkv, const float* qkv_bias, const float* bias,

@@ -149,10 +149,12 @@ __device__ __forceinline__ float prob_at(const float* plane, int w, const OutTap
 // ---- the LDS histogram [K][3] = {mask_area, original_area, both} of the panoptic kernels --------------------------------------------
 // Accumulated in LDS over the tiles a workgroup walks, it reaches global memory once per workgroup.  All three are called by every
 // thread of a 256-thread workgroup.
-__device__ __forceinline__ void hist_zero(int* hist, int K) {
-  for (int i = threadIdx.x; i < 3 * K; i += 256) hist[i] = 0;
+// (the _n forms: a histogram of n cells of any layout -- pair_count.hip's [G + 1][P + 1])
+__device__ __forceinline__ void hist_zero_n(int* hist, int n) {
+  for (int i = threadIdx.x; i < n; i += 256) hist[i] = 0;
   __syncthreads();
 }
+__device__ __forceinline__ void hist_zero(int* hist, int K) { hist_zero_n(hist, 3 * K); }
 
 // original_area of k += the lanes of this wave with `covered` set, one LDS atomic per wave (the ballot has to see every lane: the
 // caller's trip count is uniform over the workgroup)
@@ -161,11 +163,12 @@ __device__ __forceinline__ void hist_covered(int* hist, int k, bool covered) {
   if ((threadIdx.x & 63) == 0 && b) atomicAdd(&hist[3 * k + 1], (int)__popcll(b));
 }
 
-__device__ __forceinline__ void hist_flush(const int* hist, int K, int* __restrict__ counts) {
+__device__ __forceinline__ void hist_flush_n(const int* hist, int n, int* __restrict__ counts) {
   __syncthreads();
-  for (int i = threadIdx.x; i < 3 * K; i += 256)
+  for (int i = threadIdx.x; i < n; i += 256)
     if (hist[i]) atomicAdd(counts + i, hist[i]);
 }
+__device__ __forceinline__ void hist_flush(const int* hist, int K, int* __restrict__ counts) { hist_flush_n(hist, 3 * K, counts); }
 
 // ---- the kernels that the image and the video entry points share --------------------------------------------------------------------
 // grid (row segments, K): the quality counts {|U > 1|, |U > -1|} of one row of planes over rows [y0, y1) of frames 0, step, 2 step, ...

@@ -336,6 +336,8 @@ def write_vps_predictions(inputs: dict, outputs: dict, output_dir: str, categori
         img = Image.fromarray(pan_format[i])
         img.save(os.path.join(save_dir, name.split("/")[-1].split(".")[0] + ".png"))
         img.close()
+        # (evaluation/vps.py: VPSEvaluator._tables_in_process replays this order -- the segments with pixels in frame i, in
+        # `segments_infos`' order -- to map segment ids to the colour ids; it checks the replay against each entry's `area`)
         annotations.append({"segments_info": [d[i] for d in per_segment if d[i] is not None], "file_name": name.split("/")[-1]})
     return {"annotations": annotations, "video_id": video_id}
 
