@@ -808,6 +808,20 @@ int univs_video_panoptic_paint_i32(const float* M, int Q, int V, int h, int w, i
 int univs_panoptic_pair_counts(const void* gt, int gt_rgb, const void* pred, int pred_rgb, int T, int H, int W, const int32_t* gt_ids, int G,
                                const int32_t* pred_ids, int P, int32_t* counts, int32_t* first_unknown, void* stream);
 
+/* ---- scoring a video semantic result (csrc/vss_count.hip) ------------------------------------------------------------------------------
+ * gt / pred: uint8 [T, H, W], the raw VSPW mask values (0 = "others", 1..124, 255 = void) and the bytes of the prediction PNGs.  The
+ * ground truth is mapped as map_category_id does (0 -> 255, v -> v - 1, 254 -> 255; raw 255 ends as 255); comparisons are on mapped values.
+ * confusion [C, C] int32 (zeroed by the caller): cell C g + p += 1 for a pixel with mapped gt g < C and prediction byte p, not clamped.  A
+ * cell >= C C is not counted; overflow [1] int32 (-1 from the caller) = the largest such cell (np.bincount(...).reshape fails there).
+ * windows [T, 2, 2] int32 (zeroed by the caller): [i][n = 8, 16][den, num] += the pixels whose mapped gt is equal over frames i .. i + n - 1
+ * and those whose prediction is equal over them too; entries whose window does not fit stay zero.
+ * C C <= 16384 and T <= 1024 (LDS), T H W < 2^31 - 4, both maps dword-aligned; else UNIVS_ERR_NOT_IMPLEMENTED.  The maps are read in
+ * whole dwords: T H W bytes that are no multiple of 4 must be readable up to the next dword (any device allocation is).
+ * Replaces: Evaluator._generate_matrix per frame (univs/evaluation/eval_utils_vss.py:96-105), map_category_id and get_common per window
+ * (vss_evaluation.py:226-251; eval_miou_vss.py:48-70, eval_vc_perclip_vss.py:33-50). */
+int univs_vss_video_counts(const uint8_t* gt, const uint8_t* pred, int T, int H, int W, int num_classes, int32_t* confusion,
+                           int32_t* windows, int32_t* overflow, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -89,6 +89,7 @@ int video_panoptic_counts_i32(const float*, int, int, int, int, int, int, int, i
 int video_panoptic_paint_i32(const float*, int, int, int, int, int, int, int, int, const int*, int, const int*, const int*, int, int, int*,
                              hipStream_t);
 int panoptic_pair_counts(const void*, int, const void*, int, int, int, int, const int*, int, const int*, int, int*, int*, hipStream_t);
+int vss_video_counts(const unsigned char*, const unsigned char*, int, int, int, int, int*, int*, int*, hipStream_t);
 int prompt_tokens_f32(const float*, const long long*, const float*, const long long*, const float*, const float*, const long long*,
                       const uint8_t*, const uint8_t*, const float*, const long long*, int, int, int, int, int, int, int, float*, float*,
                       uint8_t*, hipStream_t);
@@ -1266,6 +1267,22 @@ int univs_panoptic_pair_counts(const void* gt, int gt_rgb, const void* pred, int
                      panoptic_pair_counts(gt, gt_rgb, pred, pred_rgb, T, H, W, gt_ids, G, pred_ids, P, counts, first_unknown,
                                           static_cast<hipStream_t>(stream)),
                      "G, P <= 1024, (G + 1)(P + 1) <= 16384, T <= 65535, H W < 2^31, dword-aligned maps");
+}
+
+int univs_vss_video_counts(const uint8_t* gt, const uint8_t* pred, int T, int H, int W, int num_classes, int32_t* confusion,
+                           int32_t* windows, int32_t* overflow, void* stream) {
+  clear_sticky_error();
+  if (T < 1 || H < 1 || W < 1 || num_classes < 1) {      // (any size beyond the kernel's is "not covered", not an error)
+    set_error("univs_vss_video_counts: bad dimensions T=%d H=%d W=%d num_classes=%d", T, H, W, num_classes);
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  if (!gt || !pred || !confusion || !windows || !overflow) {
+    set_error("univs_vss_video_counts: NULL data pointer");
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  return not_covered("univs_vss_video_counts",
+                     vss_video_counts(gt, pred, T, H, W, num_classes, confusion, windows, overflow, static_cast<hipStream_t>(stream)),
+                     "num_classes^2 <= 16384, T <= 1024, T H W < 2^31 - 4, dword-aligned maps");
 }
 
 int univs_window_attention_image_f32(const float* qkv, const float* qkv_bias, const float* bias,
