@@ -21,6 +21,34 @@ def _hipcc():
     return None
 
 
+# 64-bit FNV-1a over the raw bytes of the tables the kernel reads (lv, tiles, pieces, qtab, then the case's segs and begin;
+# for a schedule line: segs and begin), one per case and schedule line, as built by the two table builders BEFORE they became
+# one (csrc/msda_window_geom.h): the builder must keep producing these bytes.  Recorded once; never regenerate them from the
+# code under test.
+TABLE_DIGESTS = {
+    "cfg1": "585ed0474792a27a",
+    "cfg1-contig": "f36d75080b8b464a",
+    "ragged": "512995eb22196ba2",
+    "L4-fine-first": "a00fc8e997fd1a2e",
+    "L1": "b4173312108ea82c",
+    "L2-tiny-halo": "8a4a4b382a4d3a9c",
+    "two-px": "6541d2e1c87bda3d",
+    "cfg2-slice": "3613ec620046c7ce",
+    "cfg2-w16h6": "9529081976f51427",
+    "cfg5-slice": "a3dc56397a47a419",
+    "schedule cfg2 N=5 policy 0": "4aa431d4583c53cc",
+    "schedule cfg2 N=5 policy 1": "3194d479775be372",
+    "schedule cfg2 N=1 policy 0": "e3f575a80933b55a",
+    "schedule cfg2 N=1 policy 1": "2c6d0fa65202b515",
+    "schedule cfg5 N=10 policy 0": "b948be8436d142e9",
+    "schedule cfg5 N=10 policy 1": "cc2c62857ad96199",
+    "schedule cfg1 N=2 policy 0": "0e0a8e47dfb4140a",
+    "schedule cfg1 N=2 policy 1": "e3a1520e68012cd5",
+    "schedule cfg2 N=40 policy 0": "5ce3a33c3769d52b",
+    "schedule cfg2 N=40 policy 1": "c6bbd9a9217d91d7",
+}
+
+
 @pytest.mark.skipif(_hipcc() is None, reason="hipcc not found")
 def test_heads_data_flow_and_schedules_on_the_host(tmp_path):
     exe = str(tmp_path / "heads_emulate")
@@ -40,3 +68,5 @@ def test_heads_data_flow_and_schedules_on_the_host(tmp_path):
     for l in sched:      # every schedule covers every tile once and is balanced to one tile
         m = re.search(r": ok, steps total (\d+) \(want (\d+)\), max per workgroup (\d+) \(ideal ([0-9.]+)\)", l)
         assert m and m.group(1) == m.group(2) and int(m.group(3)) <= float(m.group(4)) + 1.0, l
+    got = dict(re.match(r"tables (.+) ([0-9a-f]{16})$", l).groups() for l in out.splitlines() if l.startswith("tables "))
+    assert got == TABLE_DIGESTS

@@ -20,6 +20,22 @@ def _hipcc():
     return None
 
 
+# 64-bit FNV-1a over the raw bytes of the tables the kernel reads (lv, tiles, pieces, qtab), one per case, as built by the two
+# table builders BEFORE they became one (csrc/msda_window_geom.h): the builder must keep producing these bytes.  Recorded
+# once; never regenerate them from the code under test.
+TABLE_DIGESTS = {
+    "cfg1": "945dfa2d23b3cc40",
+    "ragged": "b8576e2478ec79c1",
+    "L4-fine-first": "a67cec007e69a3dd",
+    "L1": "bf4672240d952623",
+    "L2-tiny-halo": "30be6676f8fa2dd2",
+    "two-px": "0de186ca39af1d7d",
+    "cfg2-slice": "1b5d4626868a3f2f",
+    "cfg2-th6": "2a58a9671c184582",
+    "cfg5-slice": "bc2a3d81a3880946",
+}
+
+
 @pytest.mark.skipif(_hipcc() is None, reason="hipcc not found")
 def test_strips_data_flow_on_the_host(tmp_path):
     exe = str(tmp_path / "strips_emulate")
@@ -33,3 +49,5 @@ def test_strips_data_flow_on_the_host(tmp_path):
         assert m, l
         assert float(m.group(1)) < 2e-5 and all(int(m.group(i)) == 0 for i in range(2, 6)), l
     assert any(l.startswith("cfg2-slice") for l in rows) and any(l.startswith("cfg5-slice") for l in rows)
+    got = dict(re.match(r"tables (.+) ([0-9a-f]{16})$", l).groups() for l in out.splitlines() if l.startswith("tables "))
+    assert got == TABLE_DIGESTS

@@ -2,41 +2,12 @@
 // records -> gathers in the lane-specific corner / chunk order -> point reduction -> output channels; global fallback for
 // samples that leave the window) against a plain double-precision bilinear reference (ms_deform_im2col_cuda.cuh:38-89,
 // 242-304) on the STANDARD layouts.  It compiles the SAME table builder and record function the kernel uses
-// (csrc/msda_strips_geom.h: s5_build_host, s5_record), re-creates the head-major operand layouts the Linear epilogues
+// (csrc/msda_strips_geom.h over csrc/msda_window_geom.h: s5_build_host, s5_record), re-creates the head-major operand layouts the Linear epilogues
 // write, and checks on the way that (a) every ds_read_b128 lane group of the gather touches 16 different 16-byte slots
 // (bank-conflict-free by construction), (b) no LDS byte is read before the current window wrote it (stale circular rows).
 //   hipcc -O2 -std=c++17 -I include tools/strips_emulate.cpp -o /tmp/strips_emulate && /tmp/strips_emulate
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <random>
-#include <vector>
-
 #include "../univs_amd/csrc/msda_strips_geom.h"
-
-namespace univs { void set_error(const char*, ...) {} }
-using namespace univs;
-
-struct Case { const char* name; std::vector<std::pair<int, int>> shapes; int N, M, TH, TW, R; float off_std; int nwg; };
-
-static double ref_sample(const std::vector<float>& value, int S, int M, int n, int m, int start, int H, int W, float x, float y,
-                         double aw, int ch) {
-  const float him = y * H - 0.5f, wim = x * W - 0.5f;
-  if (!(him > -1 && wim > -1 && him < H && wim < W)) return 0.0;
-  const int h0 = (int)floorf(him), w0 = (int)floorf(wim);
-  const double lh = him - h0, lw = wim - w0;
-  auto v = [&](int h, int w) -> double {
-    if (h < 0 || w < 0 || h >= H || w >= W) return 0.0;
-    return value[(((size_t)n * S + start + (size_t)h * W + w) * M + m) * 32 + ch];
-  };
-  return aw * ((1 - lh) * (1 - lw) * v(h0, w0) + (1 - lh) * lw * v(h0, w0 + 1) + lh * (1 - lw) * v(h0 + 1, w0) + lh * lw * v(h0 + 1, w0 + 1));
-}
-
-// the ds_read_b128 lane groups of gfx950 (MI355X_MICROARCH.md, LDS table)
-static const int GROUPS[4][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
-                                  {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31},
-                                  {32, 33, 34, 35, 44, 45, 46, 47, 52, 53, 54, 55, 56, 57, 58, 59},
-                                  {36, 37, 38, 39, 40, 41, 42, 43, 48, 49, 50, 51, 60, 61, 62, 63}};
+#include "msda_emulate_common.h"
 
 int main() {
   std::vector<Case> cases = {
@@ -52,56 +23,16 @@ int main() {
   };
   int bad_total = 0;
   for (const Case& c : cases) {
-    const int L = (int)c.shapes.size(), P = 4;
-    LevelTable lv{};
-    int S = 0, fine = 0;
-    for (int l = 0; l < L; ++l) {
-      lv.H[l] = c.shapes[l].first; lv.W[l] = c.shapes[l].second; lv.start[l] = S;
-      S += lv.H[l] * lv.W[l];
-      if (lv.H[l] * lv.W[l] > lv.H[fine] * lv.W[fine]) fine = l;
-    }
-    const int N = c.N, M = c.M;
-    std::mt19937 rng(1234);
-    std::normal_distribution<float> nd(0.f, 1.f);
-    // standard layouts: value [N][S][M][32]; raw projections: offsets [N][S][M][L][P][2] (pixels of the target level), logits
-    // [N][S][M][L][P]; reference points [S][L][2] (pixel centres of the query's own level)
-    std::vector<float> value((size_t)N * S * M * 32), off((size_t)N * S * M * L * P * 2), logit((size_t)N * S * M * L * P), ref((size_t)S * L * 2);
-    for (auto& v : value) v = nd(rng);
-    for (auto& v : off) v = nd(rng) * c.off_std;
-    for (auto& v : logit) v = nd(rng);
-    for (int lq = 0; lq < L; ++lq)
-      for (int i = 0; i < lv.H[lq] * lv.W[lq]; ++i)
-        for (int l = 0; l < L; ++l) {
-          ref[((size_t)(lv.start[lq] + i) * L + l) * 2 + 0] = ((i % lv.W[lq]) + 0.5f) / lv.W[lq];
-          ref[((size_t)(lv.start[lq] + i) * L + l) * 2 + 1] = ((i / lv.W[lq]) + 0.5f) / lv.H[lq];
-        }
-    // every 11th query: far offsets (misses, partly outside the image)
-    for (int n = 0; n < N; ++n)
-      for (int q = 0; q < S; ++q)
-        if (q % 11 == 5)
-          for (size_t i = 0; i < (size_t)M * L * P * 2; ++i) off[((size_t)n * S + q) * M * L * P * 2 + i] *= 5.f;
-    int order[4] = {0, 1, 2, 3};
-    std::sort(order, order + L, [&](int a, int b) {
-      const long long sa = (long long)lv.H[a] * lv.W[a], sb = (long long)lv.H[b] * lv.W[b];
-      return sa != sb ? sa > sb : a < b;
-    });
-    // head-major operands as the Linear epilogues write them
-    std::vector<float> vhm((size_t)N * M * 2 * S * 16), qhm((size_t)N * M * S * P * 3 * L);
+    const Operands o = make_operands(c);
+    const LevelTable& lv = o.lv;
+    const int L = o.L, S = o.S, fine = o.fine, N = o.N, M = o.M;
+    // head-major value as the Linear epilogue writes it: [N][M][2 halves][S][16]
+    std::vector<float> vhm((size_t)N * M * 2 * S * 16);
     for (int n = 0; n < N; ++n)
       for (int s = 0; s < S; ++s)
-        for (int m = 0; m < M; ++m) {
+        for (int m = 0; m < M; ++m)
           for (int ch = 0; ch < 32; ++ch)
-            vhm[((((size_t)n * M + m) * 2 + ch / 16) * S + s) * 16 + ch % 16] = value[(((size_t)n * S + s) * M + m) * 32 + ch];
-          for (int p = 0; p < P; ++p) {   // levels in SLOT order (largest first, ties by index), as ops.msda_pack_head_major
-            float* row = &qhm[((((size_t)n * M + m) * S + s) * P + p) * 3 * L];
-            for (int kk = 0; kk < L; ++kk) {
-              const int l = order[kk];
-              row[2 * kk] = off[(((((size_t)n * S + s) * M + m) * L + l) * P + p) * 2];
-              row[2 * kk + 1] = off[(((((size_t)n * S + s) * M + m) * L + l) * P + p) * 2 + 1];
-              row[2 * L + kk] = logit[((((size_t)n * S + s) * M + m) * L + l) * P + p];
-            }
-          }
-        }
+            vhm[((((size_t)n * M + m) * 2 + ch / 16) * S + s) * 16 + ch % 16] = o.value[(((size_t)n * S + s) * M + m) * 32 + ch];
     S5Host g;
     for (int TH = c.TH; TH >= 2; TH -= 2) {   // as msda_forward_strips_f32 chooses the tile height
       s5_build_host(lv, L, fine, TH, c.TW, c.R, g);
@@ -109,6 +40,7 @@ int main() {
       g.ok = false;
     }
     if (!g.ok) { printf("%-14s tables not ok (qmax %lld lds %zu)\n", c.name, g.qmax, g.lds); ++bad_total; continue; }
+    printf("tables %s %016llx\n", c.name, table_digest(g));
     const unsigned nitems = (unsigned)((long long)N * M * 2 * g.ntiles);
     std::vector<float> out((size_t)N * S * M * 32, 0.f), cnt((size_t)N * S * M * 32, 0.f);
     long long conflicts = 0, stale = 0, misses = 0, samples = 0, reads = 0, inexact_div = 0;
@@ -156,29 +88,8 @@ int main() {
           for (auto& a : acc) for (auto& b : a) for (auto& x : b) x = 0.f;
           int qg[64];
           float xs[64][4], ys[64][4], as[64][4];
-          for (int lane = 0; lane < 64; ++lane) {
-            const int qi = lane & 15, pt = lane >> 4;
-            qg[lane] = g.qtab[(size_t)tile * S5_QCAP + wave * 16 + qi];
-            const float* row = &qhm[((((size_t)n * M + m) * S + qg[lane]) * P + pt) * 3 * L];
-            for (int kk = 0; kk < L; ++kk) {
-              const int l = g.lv.l[kk];
-              // the kernel's division: reciprocal multiply + exact-remainder correction; must equal the IEEE quotient
-              const float Wf = (float)g.lv.W[kk], Hf = (float)g.lv.H[kk];
-              if (g.lv.l[kk] != order[kk]) { printf("slot order mismatch\n"); ++bad_total; }
-              const float qx = row[2 * kk] * g.lv.rW[kk], qy = row[2 * kk + 1] * g.lv.rH[kk];
-              const float ox = fmaf(fmaf(-qx, Wf, row[2 * kk]), g.lv.rW[kk], qx), oy = fmaf(fmaf(-qy, Hf, row[2 * kk + 1]), g.lv.rH[kk], qy);
-              if (ox != row[2 * kk] / Wf || oy != row[2 * kk + 1] / Hf) ++inexact_div;
-              xs[lane][kk] = ref[((size_t)qg[lane] * L + l) * 2] + ox;
-              ys[lane][kk] = ref[((size_t)qg[lane] * L + l) * 2 + 1] + oy;
-              as[lane][kk] = row[2 * L + kk];
-            }
-          }
-          for (int qi = 0; qi < 16; ++qi) {   // softmax over the L * P logits of the query (the 4 DPP rows)
-            float mx = -INFINITY, sum = 0.f;
-            for (int pt = 0; pt < 4; ++pt) for (int kk = 0; kk < L; ++kk) mx = fmaxf(mx, as[pt * 16 + qi][kk]);
-            for (int pt = 0; pt < 4; ++pt) for (int kk = 0; kk < L; ++kk) { as[pt * 16 + qi][kk] = expf(as[pt * 16 + qi][kk] - mx); sum += as[pt * 16 + qi][kk]; }
-            for (int pt = 0; pt < 4; ++pt) for (int kk = 0; kk < L; ++kk) as[pt * 16 + qi][kk] /= sum;
-          }
+          for (int lane = 0; lane < 64; ++lane) qg[lane] = g.qtab[(size_t)tile * S5_QCAP + wave * 16 + (lane & 15)];
+          lane_inputs(o, g.lv, n, m, qg, xs, ys, as, inexact_div, bad_total);
           for (int kk = 0; kk < L; ++kk) {
             S5Rec rec[64];
             for (int lane = 0; lane < 64; ++lane) {
@@ -188,15 +99,7 @@ int main() {
             }
             for (int k = 0; k < 4; ++k)
               for (int j = 0; j < 4; ++j) {
-                for (int gr = 0; gr < 4; ++gr) {   // (a) the 16 lanes of a ds_read_b128 group hit 16 different slots
-                  unsigned seen = 0;
-                  for (int i = 0; i < 16; ++i) {
-                    const unsigned addr = rec[GROUPS[gr][i]].a[k] ^ (unsigned)(j << 4);
-                    const unsigned slot = (addr >> 4) & 15u;
-                    if (seen & (1u << slot)) ++conflicts;
-                    seen |= 1u << slot;
-                  }
-                }
+                conflicts += group_conflicts(rec, k, j);   // (a) the 16 lanes of a ds_read_b128 group hit 16 different slots
                 for (int lane = 0; lane < 64; ++lane) {
                   const unsigned addr = rec[lane].a[k] ^ (unsigned)(j << 4);
                   if (addr + 16 > g.lds || (addr & 15)) { printf("%s: LDS read out of range / misaligned\n", c.name); ++bad_total; continue; }
@@ -209,7 +112,7 @@ int main() {
                 }
               }
             for (int lane = 0; lane < 64; ++lane)
-              if (!rec[lane].inwin && as[lane][kk] != 0.f && s5_inband(xs[lane][kk], ys[lane][kk], (float)g.lv.H[kk], (float)g.lv.W[kk])) {   // global fallback
+              if (!rec[lane].inwin && as[lane][kk] != 0.f && win_inband(xs[lane][kk], ys[lane][kk], (float)g.lv.H[kk], (float)g.lv.W[kk])) {   // global fallback
                 ++misses;
                 const Footprint fp = footprint(g.lv.H[kk], g.lv.W[kk], xs[lane][kk], ys[lane][kk], as[lane][kk]);
                 const float* vl = &vhm[((size_t)hd * S + g.lv.start[kk]) * 16];
@@ -244,31 +147,8 @@ int main() {
         }
       }
     }
-    // compare with the double-precision reference on the standard layouts
-    double maxerr = 0;
     long long uncovered = 0;
-    for (int n = 0; n < N; ++n)
-      for (int q = 0; q < S; q += (S > 6000 ? 7 : 1))
-        for (int m = 0; m < M; ++m) {
-          double lg[4][4], mx = -1e30, sum = 0;
-          for (int l = 0; l < L; ++l) for (int p = 0; p < P; ++p) { lg[l][p] = logit[((((size_t)n * S + q) * M + m) * L + l) * P + p]; mx = std::max(mx, lg[l][p]); }
-          for (int l = 0; l < L; ++l) for (int p = 0; p < P; ++p) { lg[l][p] = exp((double)(float)expf((float)(lg[l][p] - mx)) > 0 ? lg[l][p] - mx : lg[l][p] - mx); lg[l][p] = exp(lg[l][p] - 0.0); }
-          // (plain double softmax)
-          sum = 0;
-          for (int l = 0; l < L; ++l) for (int p = 0; p < P; ++p) { lg[l][p] = exp((double)logit[((((size_t)n * S + q) * M + m) * L + l) * P + p] - mx); sum += lg[l][p]; }
-          for (int ch = 0; ch < 32; ch += 5) {
-            double r = 0;
-            for (int l = 0; l < L; ++l)
-              for (int p = 0; p < P; ++p) {
-                const float x = ref[((size_t)q * L + l) * 2] + off[(((((size_t)n * S + q) * M + m) * L + l) * P + p) * 2] / (float)lv.W[l];
-                const float y = ref[((size_t)q * L + l) * 2 + 1] + off[(((((size_t)n * S + q) * M + m) * L + l) * P + p) * 2 + 1] / (float)lv.H[l];
-                r += ref_sample(value, S, M, n, m, lv.start[l], lv.H[l], lv.W[l], x, y, lg[l][p] / sum, ch);
-              }
-            const size_t o = (((size_t)n * S + q) * M + m) * 32 + ch;
-            if (cnt[o] < 1.f) ++uncovered;
-            maxerr = std::max(maxerr, fabs(r - (double)out[o]));
-          }
-        }
+    const double maxerr = compare_with_reference(o, out, cnt, uncovered);
     long long zero_cnt = 0;
     for (float v : cnt) zero_cnt += v < 1.f;
     const bool ok = maxerr < 2e-5 && conflicts == 0 && stale == 0 && zero_cnt == 0 && uncovered == 0 && inexact_div == 0;

@@ -1385,74 +1385,58 @@ int univs_linear_blocked_f32(const float* x, const float* weight, const float* b
   return rc;
 }
 
-int univs_msda_forward_strips_f32(const float* value_hm, const int64_t* spatial_shapes, const int64_t* level_start,
-                                  const float* proj_hm, const float* ref_points, long long ref_batch_stride, int N, int S, int M,
-                                  int D, int L, int Lq, int P, float* out, void* stream) {
+// The two head-major MSDA entry points differ in the kernel (`forward`, generation `gen`) and in what it covers (`covers`).
+typedef int (*MsdaHeadMajorFn)(const float*, const LevelTable&, const float*, const float*, long long, int, int, int, int, int, int, int,
+                               float*, hipStream_t);
+static int msda_forward_head_major(const char* name, MsdaHeadMajorFn forward, int gen, const char* covers, const float* value_hm,
+                                   const int64_t* spatial_shapes, const int64_t* level_start, const float* proj_hm,
+                                   const float* ref_points, long long ref_batch_stride, int N, int S, int M, int D, int L, int Lq, int P,
+                                   float* out, void* stream) {
   if (N < 0 || S < 0 || M < 1 || D < 0 || Lq < 0 || P < 1 || L < 1 || L > UNIVS_MAX_LEVELS || ref_batch_stride < 0) {
-    set_error("univs_msda_forward_strips_f32: bad dimensions N=%d S=%d M=%d D=%d L=%d Lq=%d P=%d", N, S, M, D, L, Lq, P);
+    set_error("%s: bad dimensions N=%d S=%d M=%d D=%d L=%d Lq=%d P=%d", name, N, S, M, D, L, Lq, P);
     return UNIVS_ERR_INVALID_ARGUMENT;
   }
   if ((long long)N * Lq * M * D == 0) return UNIVS_OK;
   clear_sticky_error();
   g_msda_gen = 0;
   if (!value_hm || !proj_hm || !ref_points || !out) {
-    set_error("univs_msda_forward_strips_f32: NULL data pointer");
+    set_error("%s: NULL data pointer", name);
     return UNIVS_ERR_INVALID_ARGUMENT;
   }
   LevelTable lv;
-  int rc = make_levels(spatial_shapes, level_start, L, S, &lv, "univs_msda_forward_strips_f32");
+  int rc = make_levels(spatial_shapes, level_start, L, S, &lv, name);
   if (rc != UNIVS_OK) return rc;
   if (config().msda_impl == 1) {   // the generic kernel was forced: it has no head-major variant, the caller takes the two-operator path
-    set_error("univs_msda_forward_strips_f32: generic implementation forced (univs_msda_set_impl(1))");
+    set_error("%s: generic implementation forced (univs_msda_set_impl(1))", name);
     return UNIVS_ERR_NOT_IMPLEMENTED;
   }
-  rc = msda_forward_strips_f32(value_hm, lv, proj_hm, ref_points, ref_batch_stride, N, S, M, D, L, Lq, P, out,
-                               static_cast<hipStream_t>(stream));
+  rc = forward(value_hm, lv, proj_hm, ref_points, ref_batch_stride, N, S, M, D, L, Lq, P, out, static_cast<hipStream_t>(stream));
   if (rc > 0) {
     g_msda_last = 2;
-    g_msda_gen = 5;
+    g_msda_gen = gen;
     return UNIVS_OK;
   }
   if (rc == 0) {
-    set_error("univs_msda_forward_strips_f32: geometry not covered (D == 32, P == 4, 1 <= L <= 4, Lq == S, windows within 80 KB of LDS)");
+    set_error("%s: geometry not covered (%s)", name, covers);
     return UNIVS_ERR_NOT_IMPLEMENTED;
   }
   return rc;
 }
 
-int univs_msda_forward_heads_f32(const float* value_hm, const int64_t* spatial_shapes, const int64_t* level_start,
+int univs_msda_forward_strips_f32(const float* value_hm, const int64_t* spatial_shapes, const int64_t* level_start,
                                   const float* proj_hm, const float* ref_points, long long ref_batch_stride, int N, int S, int M,
                                   int D, int L, int Lq, int P, float* out, void* stream) {
-  if (N < 0 || S < 0 || M < 1 || D < 0 || Lq < 0 || P < 1 || L < 1 || L > UNIVS_MAX_LEVELS || ref_batch_stride < 0) {
-    set_error("univs_msda_forward_heads_f32: bad dimensions N=%d S=%d M=%d D=%d L=%d Lq=%d P=%d", N, S, M, D, L, Lq, P);
-    return UNIVS_ERR_INVALID_ARGUMENT;
-  }
-  if ((long long)N * Lq * M * D == 0) return UNIVS_OK;
-  clear_sticky_error();
-  g_msda_gen = 0;
-  if (!value_hm || !proj_hm || !ref_points || !out) {
-    set_error("univs_msda_forward_heads_f32: NULL data pointer");
-    return UNIVS_ERR_INVALID_ARGUMENT;
-  }
-  LevelTable lv;
-  int rc = make_levels(spatial_shapes, level_start, L, S, &lv, "univs_msda_forward_heads_f32");
-  if (rc != UNIVS_OK) return rc;
-  if (config().msda_impl == 1) {   // the generic kernel was forced: it has no head-major variant, the caller takes the two-operator path
-    set_error("univs_msda_forward_heads_f32: generic implementation forced (univs_msda_set_impl(1))");
-    return UNIVS_ERR_NOT_IMPLEMENTED;
-  }
-  rc = msda_forward_heads_f32(value_hm, lv, proj_hm, ref_points, ref_batch_stride, N, S, M, D, L, Lq, P, out,
-                               static_cast<hipStream_t>(stream));
-  if (rc > 0) {
-    g_msda_last = 2;
-    g_msda_gen = 6;
-    return UNIVS_OK;
-  }
-  if (rc == 0) {
-    set_error("univs_msda_forward_heads_f32: geometry not covered (D == 32, P == 4, 1 <= L <= 4, Lq == S, windows within 160 KB of LDS)");
-    return UNIVS_ERR_NOT_IMPLEMENTED;
-  }
-  return rc;
+  return msda_forward_head_major("univs_msda_forward_strips_f32", msda_forward_strips_f32, 5,
+                                 "D == 32, P == 4, 1 <= L <= 4, Lq == S, windows within 80 KB of LDS", value_hm, spatial_shapes,
+                                 level_start, proj_hm, ref_points, ref_batch_stride, N, S, M, D, L, Lq, P, out, stream);
+}
+
+int univs_msda_forward_heads_f32(const float* value_hm, const int64_t* spatial_shapes, const int64_t* level_start,
+                                 const float* proj_hm, const float* ref_points, long long ref_batch_stride, int N, int S, int M,
+                                 int D, int L, int Lq, int P, float* out, void* stream) {
+  return msda_forward_head_major("univs_msda_forward_heads_f32", msda_forward_heads_f32, 6,
+                                 "D == 32, P == 4, 1 <= L <= 4, Lq == S, windows within 160 KB of LDS", value_hm, spatial_shapes,
+                                 level_start, proj_hm, ref_points, ref_batch_stride, N, S, M, D, L, Lq, P, out, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,8 @@
-// Host-side tile geometry shared by the LDS-tiled MSDA kernels (msda_tiled.hip, msda_tiled2.hip).
+// Host side shared by the LDS-tiled MSDA kernels (msda_tiled2.hip, msda_strips.hip, msda_heads.hip): the tile / window intervals
+// of an axis, the launch preconditions, and the cache of per-geometry device tables with its event-deferred frees.
 #pragma once
 #include <algorithm>
+#include <array>
 #include <memory>
 #include <mutex>
 #include <utility>
@@ -19,7 +21,7 @@ static inline long long ceil_div(long long a, long long b) {  // b > 0
   return -floor_div(-a, b);
 }
 
-// ---- host-side geometry: built once per (device, level shapes, tile parameters); the 32 most recent are kept.
+// ---- generation 2's geometry: built once per (device, level shapes, tile parameters); the 32 most recent are kept.
 struct GeoKey {
   int dev, L, TH, TW, R, ring;
   long long cap_px;
@@ -45,12 +47,14 @@ struct GeoUse {
 };
 struct GeoEntry {
   GeoKey key;
-  int4* table;       // device
+  int4* table = nullptr;   // device
   int tiles_y, tiles_x;
   long long qmax;    // max queries of a tile
   long long win_px;  // max window pixels of a (tile, level)
   long long lvl_px[UNIVS_MAX_LEVELS];   // ... per level
+  unsigned long long stamp = 0;
   GeoUse use;        // per-stream "last launch" events + the capture pin (geo_mark_use)
+  std::array<void*, 1> tables() const { return {table}; }
 };
 
 // Lifetime of a cached geometry: callers hold a shared_ptr for the duration of their launch call (an eviction by another host
@@ -128,79 +132,142 @@ static void axis_entry(int t, int ntile, int T, int Nq, int Nf, int R, int cap, 
   e.x = (int)lo; e.y = (int)(hi - lo); e.z = (int)w0; e.w = (int)wn;
 }
 
-static void geo_free(GeoEntry* e) {
+// ---- launch preconditions
+// The level table is dense from 0 and covers the S pixels, every level is at least 2 x 2; *fine = the largest level (the
+// first of equals).
+static inline bool dense_levels(const LevelTable& lv, int L, int S, int* fine) {
+  long long expect = 0;
+  *fine = 0;
+  for (int l = 0; l < L; ++l) {
+    if (lv.start[l] != expect || lv.H[l] < 2 || lv.W[l] < 2) return false;
+    expect += (long long)lv.H[l] * lv.W[l];
+    if ((long long)lv.H[l] * lv.W[l] > (long long)lv.H[*fine] * lv.W[*fine]) *fine = l;
+  }
+  return expect == S;
+}
+// Compute units of the current device (256 if it cannot be asked), queried once per device.
+static inline int cu_count() {
+  static std::mutex mu;
+  static std::vector<int> by_dev;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0) {
+    (void)hipGetLastError();
+    return 256;
+  }
+  std::lock_guard<std::mutex> lock(mu);
+  if ((size_t)dev >= by_dev.size()) by_dev.resize((size_t)dev + 1, 0);
+  if (by_dev[dev] == 0) {
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) {
+      (void)hipGetLastError();
+      v = 256;
+    }
+    by_dev[dev] = v;
+  }
+  return by_dev[dev];
+}
+
+// ---- the cache of per-geometry device tables
+template <class T>
+static bool upload(T** dst, const std::vector<T>& src) {
+  return hipMalloc(reinterpret_cast<void**>(dst), src.size() * sizeof(T)) == hipSuccess &&
+         hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
+}
+// The deleter of every cache entry: frees the device pointers the entry lists in tables() (null ones skipped).
+template <class E>
+static void geo_free(E* e) {
   if (!e) return;
-  if (e->table) (void)hipFree(e->table);
+  for (void* p : e->tables())
+    if (p) (void)hipFree(p);
   e->use.destroy();
   delete e;
 }
+// One cache per kernel generation (a function-local static of its lookup function).  Key: `int dev` (filled in here) and
+// operator==.  Entry: `Key key`, `GeoUse use`, `unsigned long long stamp`, tables().  At CAP entries a new one retires the
+// unpinned entry OF THIS DEVICE with the smallest stamp (image datasets: many resolutions) -- the least recently used one if
+// LRU, else the oldest.  `build(e)` fills a fresh entry and uploads its tables; false = an upload failed: the entry is freed
+// and get() returns nullptr, as it does for a miss while `st` is being captured.
+template <class Key, class Entry, size_t CAP, bool LRU>
+class GeoCache {
+ public:
+  template <class Build>
+  std::shared_ptr<Entry> get(Key key, hipStream_t st, Build&& build) {
+    if (hipGetDevice(&key.dev) != hipSuccess) return nullptr;
+    std::lock_guard<std::mutex> lock(mu_);
+    for (size_t i = 0; i < retired_.size();)                      // evicted earlier: free what the GPU has finished with
+      if (geo_idle(retired_[i])) retired_.erase(retired_.begin() + i);
+      else ++i;
+    for (const auto& e : cache_)
+      if (e->key == key) {
+        if (LRU) e->stamp = ++clock_;
+        return e;
+      }
+    if (geo_capturing(st)) return nullptr;
+    std::shared_ptr<Entry> sp(new Entry(), geo_free<Entry>);
+    sp->key = key;
+    sp->stamp = ++clock_;
+    if (!build(*sp)) {
+      (void)hipGetLastError();
+      return nullptr;
+    }
+    if (cache_.size() >= CAP) {
+      size_t victim = cache_.size();
+      for (size_t i = 0; i < cache_.size(); ++i)
+        if (cache_[i]->key.dev == key.dev && !geo_pinned(cache_[i]) && (victim == cache_.size() || cache_[i]->stamp < cache_[victim]->stamp))
+          victim = i;
+      if (victim < cache_.size()) {
+        retired_.push_back(cache_[victim]);
+        cache_.erase(cache_.begin() + victim);
+      }
+    }
+    cache_.push_back(sp);
+    return sp;
+  }
+
+ private:
+  std::mutex mu_;
+  std::vector<std::shared_ptr<Entry>> cache_, retired_;
+  unsigned long long clock_ = 0;
+};
 
 static std::shared_ptr<GeoEntry> geometry(const LevelTable& lv, int L, int fine, int TH, int TW, int R, long long cap_px,
                                           hipStream_t st, int ring = 1) {
-  static std::mutex mu;
-  static std::vector<std::shared_ptr<GeoEntry>> cache, retired;
+  static GeoCache<GeoKey, GeoEntry, 32, /*LRU=*/false> cache;
   GeoKey key{};
-  if (hipGetDevice(&key.dev) != hipSuccess) return nullptr;
   key.L = L; key.TH = TH; key.TW = TW; key.R = R; key.ring = ring; key.cap_px = cap_px;
   for (int l = 0; l < L; ++l) { key.H[l] = lv.H[l]; key.W[l] = lv.W[l]; }
-  std::lock_guard<std::mutex> lock(mu);
-  for (size_t i = 0; i < retired.size();)                       // evicted earlier: free what the GPU has finished with
-    if (geo_idle(retired[i])) retired.erase(retired.begin() + i);
-    else ++i;
-  for (const auto& e : cache)
-    if (e->key == key) return e;
-  if (geo_capturing(st)) return nullptr;
-
-  GeoEntry* ge = new GeoEntry();
-  ge->key = key;
-  ge->tiles_y = (lv.H[fine] + TH - 1) / TH;
-  ge->tiles_x = (lv.W[fine] + TW - 1) / TW;
-  std::vector<int4> tab((size_t)L * (ge->tiles_x + ge->tiles_y));
-  for (int l = 0; l < L; ++l) {
-    for (int tx = 0; tx < ge->tiles_x; ++tx)
-      axis_entry(tx, ge->tiles_x, TW, lv.W[l], lv.W[fine], R, UNIVS_MSDA_WIN_EDGE_MAX, ring, tab[(size_t)l * ge->tiles_x + tx]);
-    for (int ty = 0; ty < ge->tiles_y; ++ty)
-      axis_entry(ty, ge->tiles_y, TH, lv.H[l], lv.H[fine], R, UNIVS_MSDA_WIN_EDGE_MAX, ring,
-                 tab[(size_t)L * ge->tiles_x + (size_t)l * ge->tiles_y + ty]);
-  }
-  // windows must fit the LDS carve: shrink rows where a (tile, level) would not (samples beyond go
-  // through the global fallback, results unchanged)
-  ge->qmax = 0; ge->win_px = 4;
-  for (int l = 0; l < UNIVS_MAX_LEVELS; ++l) ge->lvl_px[l] = 0;
-  for (int l = 0; l < L; ++l) {
-    int mw = 2, mqx = 0, mqy = 0;
-    for (int tx = 0; tx < ge->tiles_x; ++tx) {
-      mw = std::max(mw, tab[(size_t)l * ge->tiles_x + tx].w);
-      mqx = std::max(mqx, tab[(size_t)l * ge->tiles_x + tx].y);
+  return cache.get(key, st, [&](GeoEntry& ge) {
+    ge.tiles_y = (lv.H[fine] + TH - 1) / TH;
+    ge.tiles_x = (lv.W[fine] + TW - 1) / TW;
+    std::vector<int4> tab((size_t)L * (ge.tiles_x + ge.tiles_y));
+    for (int l = 0; l < L; ++l) {
+      for (int tx = 0; tx < ge.tiles_x; ++tx)
+        axis_entry(tx, ge.tiles_x, TW, lv.W[l], lv.W[fine], R, UNIVS_MSDA_WIN_EDGE_MAX, ring, tab[(size_t)l * ge.tiles_x + tx]);
+      for (int ty = 0; ty < ge.tiles_y; ++ty)
+        axis_entry(ty, ge.tiles_y, TH, lv.H[l], lv.H[fine], R, UNIVS_MSDA_WIN_EDGE_MAX, ring,
+                   tab[(size_t)L * ge.tiles_x + (size_t)l * ge.tiles_y + ty]);
     }
-    for (int ty = 0; ty < ge->tiles_y; ++ty) {
-      int4& e = tab[(size_t)L * ge->tiles_x + (size_t)l * ge->tiles_y + ty];
-      e.w = (int)std::max<long long>(2, std::min<long long>(e.w, cap_px / mw));
-      mqy = std::max(mqy, e.y);
-      ge->win_px = std::max<long long>(ge->win_px, (long long)mw * e.w);
-      ge->lvl_px[l] = std::max<long long>(ge->lvl_px[l], (long long)mw * e.w);
-    }
-    ge->qmax += (long long)mqx * mqy;
-  }
-  ge->table = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&ge->table), tab.size() * sizeof(int4)) != hipSuccess ||
-      hipMemcpy(ge->table, tab.data(), tab.size() * sizeof(int4), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipGetLastError();
-    geo_free(ge);
-    return nullptr;
-  }
-  std::shared_ptr<GeoEntry> sp(ge, geo_free);
-  if (cache.size() >= 32) {   // bounded (image datasets: many resolutions): retire the oldest unpinned entry OF THIS DEVICE
-    for (size_t i = 0; i < cache.size(); ++i)
-      if (cache[i]->key.dev == key.dev && !geo_pinned(cache[i])) {
-        retired.push_back(cache[i]);
-        cache.erase(cache.begin() + i);
-        break;
+    // windows must fit the LDS carve: shrink rows where a (tile, level) would not (samples beyond go
+    // through the global fallback, results unchanged)
+    ge.qmax = 0; ge.win_px = 4;
+    for (int l = 0; l < UNIVS_MAX_LEVELS; ++l) ge.lvl_px[l] = 0;
+    for (int l = 0; l < L; ++l) {
+      int mw = 2, mqx = 0, mqy = 0;
+      for (int tx = 0; tx < ge.tiles_x; ++tx) {
+        mw = std::max(mw, tab[(size_t)l * ge.tiles_x + tx].w);
+        mqx = std::max(mqx, tab[(size_t)l * ge.tiles_x + tx].y);
       }
-  }
-  cache.push_back(sp);
-  return sp;
+      for (int ty = 0; ty < ge.tiles_y; ++ty) {
+        int4& e = tab[(size_t)L * ge.tiles_x + (size_t)l * ge.tiles_y + ty];
+        e.w = (int)std::max<long long>(2, std::min<long long>(e.w, cap_px / mw));
+        mqy = std::max(mqy, e.y);
+        ge.win_px = std::max<long long>(ge.win_px, (long long)mw * e.w);
+        ge.lvl_px[l] = std::max<long long>(ge.lvl_px[l], (long long)mw * e.w);
+      }
+      ge.qmax += (long long)mqx * mqy;
+    }
+    return upload(&ge.table, tab);
+  });
 }
-
 
 }  // namespace univs

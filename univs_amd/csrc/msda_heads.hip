@@ -196,7 +196,7 @@ __global__ __launch_bounds__(64 * S6_NW, 2) void msda_fwd_heads(S6Args a, S6Leve
       for (int k = 0; k < 4; ++k) { r.ca[4 * kk + k] = rec.a[k]; r.cw[4 * kk + k] = rec.w[k]; }
       r.mm[kk] = __ballot(!rec.inwin);
       if (r.mm[kk] != 0)
-        r.mm[kk] = __ballot(!rec.inwin && in.a[kk] != 0.f && s6_inband(in.x[kk], in.y[kk], Hf[kk], Wf[kk]));
+        r.mm[kk] = __ballot(!rec.inwin && in.a[kk] != 0.f && win_inband(in.x[kk], in.y[kk], Hf[kk], Wf[kk]));
     }
   };
   // sum the 4 points (DPP rows) of every query and store: after the two swap rounds row r of the wave holds the finished
@@ -500,72 +500,32 @@ struct S6Geo {
   bool ok = false;
   unsigned long long stamp = 0;
   GeoUse use;                  // per-stream last-launch events + the capture pin (msda_geometry.h: geo_mark_use)
+  std::array<void*, 5> tables() const { return {tiles, pieces, qtable, segs, seg_begin}; }
 };
-
-static void s6_free(S6Geo* g) {
-  if (!g) return;
-  if (g->tiles) (void)hipFree(g->tiles);
-  if (g->pieces) (void)hipFree(g->pieces);
-  if (g->qtable) (void)hipFree(g->qtable);
-  if (g->segs) (void)hipFree(g->segs);
-  if (g->seg_begin) (void)hipFree(g->seg_begin);
-  g->use.destroy();
-  delete g;
-}
-
-template <class T>
-static bool s6_upload(T** dst, const std::vector<T>& src) {
-  return hipMalloc(reinterpret_cast<void**>(dst), src.size() * sizeof(T)) == hipSuccess &&
-         hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
-}
 
 // Shared ownership + event-deferred frees: see msda_geometry.h (an evicted entry is freed once nobody holds it and the last
 // launch that read its tables has completed; a cache miss during stream capture returns nullptr).
 static std::shared_ptr<S6Geo> s6_geometry(const LevelTable& lv, int L, int fine, int TH, int TW, int R, int planes, int grid,
                                           int policy, hipStream_t st) {
-  static std::mutex mu;
-  static std::vector<std::shared_ptr<S6Geo>> cache, retired;
-  static unsigned long long clock_ = 0;
-  constexpr size_t CACHE_MAX = 24;
+  static GeoCache<S6Key, S6Geo, 24, /*LRU=*/true> cache;
   S6Key key{};
-  if (hipGetDevice(&key.dev) != hipSuccess) return nullptr;
   key.L = L; key.TH = TH; key.TW = TW; key.R = R; key.planes = planes; key.grid = grid; key.policy = policy;
   for (int l = 0; l < L; ++l) { key.H[l] = lv.H[l]; key.W[l] = lv.W[l]; }
-  std::lock_guard<std::mutex> lock(mu);
-  for (size_t i = 0; i < retired.size();)
-    if (geo_idle(retired[i])) retired.erase(retired.begin() + i);
-    else ++i;
-  for (const auto& e : cache)
-    if (e->key == key) { e->stamp = ++clock_; return e; }
-  if (geo_capturing(st)) return nullptr;
-  S6Host h;
-  s6_build_host(lv, L, fine, TH, TW, R, h);
-  S6Geo* g = new S6Geo();
-  g->key = key; g->lv = h.lv; g->ntiles = h.ntiles; g->lds = h.lds; g->ok = h.ok && h.lds + 1024 <= (size_t)S6_LDS_MAX; g->stamp = ++clock_;
-  if (g->ok) {
+  return cache.get(key, st, [&](S6Geo& g) {
+    S6Host h;
+    s6_build_host(lv, L, fine, TH, TW, R, h);
+    g.lv = h.lv; g.ntiles = h.ntiles; g.lds = h.lds; g.ok = h.ok && h.lds + 1024 <= (size_t)S6_LDS_MAX;
+    if (!g.ok) return true;
     std::vector<S6Seg> segs;
     std::vector<int> begin;
     // a cold start (the whole windows instead of the entering rows) priced at 1.5 tiles
-    if (!s6_build_segments(planes, h.tiles_x, h.tiles_y, grid, policy, 1.5, segs, begin)) g->ok = false;
-    if (g->ok && (!s6_upload(&g->tiles, h.tiles) || !s6_upload(&g->pieces, h.pieces) || !s6_upload(&g->qtable, h.qtab) ||
-                  !s6_upload(&g->segs, segs) || !s6_upload(&g->seg_begin, begin))) {
-      (void)hipGetLastError();
-      s6_free(g);
-      return nullptr;
+    if (!s6_build_segments(planes, h.tiles_x, h.tiles_y, grid, policy, 1.5, segs, begin)) {
+      g.ok = false;
+      return true;
     }
-  }
-  std::shared_ptr<S6Geo> sp(g, s6_free);
-  if (cache.size() >= CACHE_MAX) {   // retire the least recently used geometry of THIS device (image datasets: many resolutions)
-    size_t lru = cache.size();
-    for (size_t i = 0; i < cache.size(); ++i)
-      if (cache[i]->key.dev == key.dev && !geo_pinned(cache[i]) && (lru == cache.size() || cache[i]->stamp < cache[lru]->stamp)) lru = i;
-    if (lru < cache.size()) {
-      retired.push_back(cache[lru]);
-      cache.erase(cache.begin() + lru);
-    }
-  }
-  cache.push_back(sp);
-  return sp;
+    return upload(&g.tiles, h.tiles) && upload(&g.pieces, h.pieces) && upload(&g.qtable, h.qtab) && upload(&g.segs, segs) &&
+           upload(&g.seg_begin, begin);
+  });
 }
 
 template <int L>
@@ -584,27 +544,13 @@ int msda_forward_heads_f32(const float* vhm, const LevelTable& lv, const float* 
   if ((long long)S * S6_DH * 4 >= (1LL << 31) || (long long)N * M >= (1LL << 30) || (long long)S * M * 128 >= (1LL << 32) ||
       (long long)S * P * 3 * L * 4 >= (1LL << 32))
     return 0;
-  long long expect = 0;
   int fine = 0;
-  for (int l = 0; l < L; ++l) {
-    if (lv.start[l] != expect || lv.H[l] < 2 || lv.W[l] < 2) return 0;
-    expect += (long long)lv.H[l] * lv.W[l];
-    if ((long long)lv.H[l] * lv.W[l] > (long long)lv.H[fine] * lv.W[fine]) fine = l;
-  }
-  if (expect != S) return 0;
+  if (!dense_levels(lv, L, S, &fine)) return 0;
 
   const UnivsConfig cfg = config();
   const int R = cfg.msda_halo > 0 ? cfg.msda_halo : 6;
   if (R < 0 || R > 64 || cfg.msda_strip_w < 0 || cfg.msda_strip_h < 0) return 0;
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) {
-      (void)hipGetLastError();
-      v = 256;
-    }
-    n_cu = v;
-  }
+  const int n_cu = cu_count();
   const int policy = cfg.msda_sched == 1 ? 0 : 1;   // default: lockstep rounds; 1: contiguous ranges (A / B runs)
   // Tilings in order of preference; the first whose tables fit (windows + dummy region within one CU's LDS, <= S6_QCAP queries per
   // tile) runs.  16 x 6 (128 queries per tile at the benchmark pyramids: every lane of the 8 waves owns a sample; 1.9 x the level's

@@ -304,7 +304,7 @@ __global__ __launch_bounds__(64 * S5_NW, 4) void msda_fwd_strips(S5Args a, S5Lev
       // global memory (lane = corner lane >> 4, channel lane & 15), sums them over the corners and hands the 16 channels
       // to the owning lane
       unsigned long long mm = __ballot(!rec.inwin);
-      if (mm != 0) mm = __ballot(!rec.inwin && in_cur.a[kk] != 0.f && s5_inband(in_cur.x[kk], in_cur.y[kk], Hf[kk], Wf[kk]));
+      if (mm != 0) mm = __ballot(!rec.inwin && in_cur.a[kk] != 0.f && win_inband(in_cur.x[kk], in_cur.y[kk], Hf[kk], Wf[kk]));
       if (mm != 0) {
         const float* vl = a.vhm + ((long long)cur.hd * S + lv.start[kk]) * DH + (lane & 15);
 #pragma unroll 1
@@ -407,63 +407,22 @@ struct S5Geo {
   bool ok = false;
   unsigned long long stamp = 0;
   GeoUse use;                  // per-stream last-launch events + the capture pin (msda_geometry.h: geo_mark_use)
+  std::array<void*, 3> tables() const { return {tiles, pieces, qtable}; }
 };
-
-static void s5_free(S5Geo* g) {
-  if (!g) return;
-  if (g->tiles) (void)hipFree(g->tiles);
-  if (g->pieces) (void)hipFree(g->pieces);
-  if (g->qtable) (void)hipFree(g->qtable);
-  g->use.destroy();
-  delete g;
-}
 
 // Shared ownership + event-deferred frees: see msda_geometry.h (an evicted entry is freed once nobody holds it and the last
 // launch that read its tables has completed; a cache miss during stream capture returns nullptr).
 static std::shared_ptr<S5Geo> s5_geometry(const LevelTable& lv, int L, int fine, int TH, int TW, int R, hipStream_t st) {
-  static std::mutex mu;
-  static std::vector<std::shared_ptr<S5Geo>> cache, retired;
-  static unsigned long long clock_ = 0;
-  constexpr size_t CACHE_MAX = 24;
+  static GeoCache<S5Key, S5Geo, 24, /*LRU=*/true> cache;
   S5Key key{};
-  if (hipGetDevice(&key.dev) != hipSuccess) return nullptr;
   key.L = L; key.TH = TH; key.TW = TW; key.R = R;
   for (int l = 0; l < L; ++l) { key.H[l] = lv.H[l]; key.W[l] = lv.W[l]; }
-  std::lock_guard<std::mutex> lock(mu);
-  for (size_t i = 0; i < retired.size();)
-    if (geo_idle(retired[i])) retired.erase(retired.begin() + i);
-    else ++i;
-  for (const auto& e : cache)
-    if (e->key == key) { e->stamp = ++clock_; return e; }
-  if (geo_capturing(st)) return nullptr;
-  S5Host h;
-  s5_build_host(lv, L, fine, TH, TW, R, h);
-  S5Geo* g = new S5Geo();
-  g->key = key; g->lv = h.lv; g->ntiles = h.ntiles; g->lds = h.lds; g->ok = h.ok; g->stamp = ++clock_;
-  if (h.ok) {
-    if (hipMalloc(reinterpret_cast<void**>(&g->tiles), h.tiles.size() * sizeof(S5Tile)) != hipSuccess ||
-        hipMemcpy(g->tiles, h.tiles.data(), h.tiles.size() * sizeof(S5Tile), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&g->pieces), h.pieces.size() * sizeof(S5Piece)) != hipSuccess ||
-        hipMemcpy(g->pieces, h.pieces.data(), h.pieces.size() * sizeof(S5Piece), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&g->qtable), h.qtab.size() * sizeof(int)) != hipSuccess ||
-        hipMemcpy(g->qtable, h.qtab.data(), h.qtab.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipGetLastError();
-      s5_free(g);
-      return nullptr;
-    }
-  }
-  std::shared_ptr<S5Geo> sp(g, s5_free);
-  if (cache.size() >= CACHE_MAX) {   // retire the least recently used geometry of THIS device (image datasets: many resolutions)
-    size_t lru = cache.size();
-    for (size_t i = 0; i < cache.size(); ++i)
-      if (cache[i]->key.dev == key.dev && !geo_pinned(cache[i]) && (lru == cache.size() || cache[i]->stamp < cache[lru]->stamp)) lru = i;
-    if (lru < cache.size()) {
-      retired.push_back(cache[lru]);
-      cache.erase(cache.begin() + lru);
-    }
-  }
-  cache.push_back(sp);
-  return sp;
+  return cache.get(key, st, [&](S5Geo& g) {
+    S5Host h;
+    s5_build_host(lv, L, fine, TH, TW, R, h);
+    g.lv = h.lv; g.ntiles = h.ntiles; g.lds = h.lds; g.ok = h.ok;
+    return !g.ok || (upload(&g.tiles, h.tiles) && upload(&g.pieces, h.pieces) && upload(&g.qtable, h.qtab));
+  });
 }
 
 template <int L>
@@ -481,14 +440,8 @@ int msda_forward_strips_f32(const float* vhm, const LevelTable& lv, const float*
   if ((long long)S * S5_DH * 4 >= (1LL << 31) || (long long)N * M * 2 >= (1LL << 30) || (long long)S * M * 128 >= (1LL << 32) ||
       (long long)S * P * 3 * L * 4 >= (1LL << 32))
     return 0;
-  long long expect = 0;
   int fine = 0;
-  for (int l = 0; l < L; ++l) {
-    if (lv.start[l] != expect || lv.H[l] < 2 || lv.W[l] < 2) return 0;
-    expect += (long long)lv.H[l] * lv.W[l];
-    if ((long long)lv.H[l] * lv.W[l] > (long long)lv.H[fine] * lv.W[fine]) fine = l;
-  }
-  if (expect != S) return 0;
+  if (!dense_levels(lv, L, S, &fine)) return 0;
 
   const UnivsConfig cfg = config();
   const int TW = cfg.msda_strip_w > 0 ? cfg.msda_strip_w : 12, R = cfg.msda_halo > 0 ? cfg.msda_halo : 6;
@@ -505,15 +458,7 @@ int msda_forward_strips_f32(const float* vhm, const LevelTable& lv, const float*
 
   const long long nb = (long long)N * M * 2 * g->ntiles;
   if (nb <= 0 || nb > 0x7fffffffLL) return 0;
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) {
-      (void)hipGetLastError();
-      v = 256;
-    }
-    n_cu = v;
-  }
+  const int n_cu = cu_count();
   const unsigned grid = (unsigned)std::min<long long>(nb, std::max(cfg.msda_grid > 0 ? cfg.msda_grid : 4 * n_cu, 1));
   S5Args a{vhm, qhm, ref, ref_batch_stride, out, N, S, M};
   switch (L) {

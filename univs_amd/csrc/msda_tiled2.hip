@@ -403,14 +403,8 @@ int msda_forward_tiled2_f32(const float* value, const LevelTable& lv, const floa
                             int S, int M, int D, int L, int Lq, int P, float* out, hipStream_t st) {
   if (D != 32 || P != 4 || L < 3 || L > 4 || Lq != S || M < 1) return 0;
   if ((long long)S * M * D * 4 >= (1LL << 31) || (long long)S * M * L * P * 8 >= (1LL << 31)) return 0;
-  long long expect = 0;
   int fine = 0;
-  for (int l = 0; l < L; ++l) {
-    if (lv.start[l] != expect || lv.H[l] < 2 || lv.W[l] < 2) return 0;
-    expect += (long long)lv.H[l] * lv.W[l];
-    if ((long long)lv.H[l] * lv.W[l] > (long long)lv.H[fine] * lv.W[fine]) fine = l;
-  }
-  if (expect != S) return 0;
+  if (!dense_levels(lv, L, S, &fine)) return 0;
 
   const UnivsConfig cfg = config();
   const int TH = 8, TW = 16;
@@ -449,15 +443,7 @@ int msda_forward_tiled2_f32(const float* value, const LevelTable& lv, const floa
 
   const long long nb = (long long)N * M * tg.tiles_y * tg.tiles_x;
   if (nb <= 0 || nb > 0x7fffffffLL) return 0;
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) {
-      (void)hipGetLastError();
-      v = 256;
-    }
-    n_cu = v;
-  }
+  const int n_cu = cu_count();
   const unsigned grid = (unsigned)std::min<long long>(nb, std::max(cfg.msda_grid > 0 ? cfg.msda_grid : n_cu, 1));
   switch (L) {
     case 3: launch_tiled2<3>(grid, (unsigned)nb, lds, st, value, lv, tg, ge->table, loc, attn, N, S, M, out); break;

@@ -243,7 +243,7 @@ def msda_prepare(proj, n_off, reference_points, spatial_shapes, num_heads, num_l
 
 def msda_level_order(spatial_shapes):
     """Slot order of the levels in the head-major projection layout of `msda_forward_strips`: by size, largest first, ties
-    by index (csrc/msda_strips_geom.h: s5_build_host)."""
+    by index (csrc/msda_window_geom.h: win_slot_order)."""
     sh = [(int(h), int(w)) for h, w in (spatial_shapes.tolist() if isinstance(spatial_shapes, torch.Tensor) else spatial_shapes)]
     return sorted(range(len(sh)), key=lambda l: (-sh[l][0] * sh[l][1], l))
 
