@@ -822,6 +822,23 @@ int univs_panoptic_pair_counts(const void* gt, int gt_rgb, const void* pred, int
 int univs_vss_video_counts(const uint8_t* gt, const uint8_t* pred, int T, int H, int W, int num_classes, int32_t* confusion,
                            int32_t* windows, int32_t* overflow, void* stream);
 
+/* ---- scoring a DAVIS-format VOS result (csrc/davis_count.hip) ---------------------------------------------------------------------------
+ * gt / pred: uint8 [T, H, W] id maps.  gt 255 is void; gt ids 1..G and pred ids 1..P are objects, every other value is background.
+ * use_void = 1 takes the void pixels out of both sides (`mask & ~void`, the unsupervised task); use_void = 0 leaves the result as it is
+ * there (the semi-supervised task passes no void mask); the gt's 255 is never an object.  radius >= 1: the disk holds dx^2 + dy^2 <= r^2,
+ * pixels outside the image contribute nothing.  All outputs int32, zeroed by the caller:
+ *   region [G, P, T, 2]  (intersection, union) of gt object i and result object j in frame t
+ *   n_gt [G, T], n_fg [P, T]  boundary pixels of each object's _seg2bmap (east / south / south-east neighbour differs; the last row
+ *                        compares east only, the last column south only, the bottom-right pixel is never boundary)
+ *   match [G, P, T, 2]   (gt boundary pixels of i inside the dilated result boundary of j, result boundary pixels of j inside the dilated
+ *                        gt boundary of i)
+ * G, P <= 32, radius <= 36 (LDS: a 4K frame's radius), T H W < 2^31; else UNIVS_ERR_NOT_IMPLEMENTED.
+ * Replaces: db_eval_iou, f_measure and _seg2bmap per (gt object, result object, frame)
+ * (univs/evaluation/davis2017_evaluation/davis2017/metrics.py:6-37, :57-119, :122-178) under the pair loops of
+ * _evaluate_semisupervised / _evaluate_unsupervised (univs/evaluation/vos_davis_evaluation.py:198-239). */
+int univs_davis_counts(const uint8_t* gt, const uint8_t* pred, int T, int H, int W, int G, int P, int radius, int use_void,
+                       int32_t* region, int32_t* n_gt, int32_t* n_fg, int32_t* match, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,7 @@ SIGNATURES = {
     "univs_video_panoptic_paint_i32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P]),
     "univs_panoptic_pair_counts": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P]),
     "univs_vss_video_counts": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "univs_davis_counts": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

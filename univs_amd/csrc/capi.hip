@@ -90,6 +90,7 @@ int video_panoptic_paint_i32(const float*, int, int, int, int, int, int, int, in
                              hipStream_t);
 int panoptic_pair_counts(const void*, int, const void*, int, int, int, int, const int*, int, const int*, int, int*, int*, hipStream_t);
 int vss_video_counts(const unsigned char*, const unsigned char*, int, int, int, int, int*, int*, int*, hipStream_t);
+int davis_counts(const unsigned char*, const unsigned char*, int, int, int, int, int, int, int, int*, int*, int*, int*, hipStream_t);
 int prompt_tokens_f32(const float*, const long long*, const float*, const long long*, const float*, const float*, const long long*,
                       const uint8_t*, const uint8_t*, const float*, const long long*, int, int, int, int, int, int, int, float*, float*,
                       uint8_t*, hipStream_t);
@@ -1283,6 +1284,22 @@ int univs_vss_video_counts(const uint8_t* gt, const uint8_t* pred, int T, int H,
   return not_covered("univs_vss_video_counts",
                      vss_video_counts(gt, pred, T, H, W, num_classes, confusion, windows, overflow, static_cast<hipStream_t>(stream)),
                      "num_classes^2 <= 16384, T <= 1024, T H W < 2^31 - 4, dword-aligned maps");
+}
+
+int univs_davis_counts(const uint8_t* gt, const uint8_t* pred, int T, int H, int W, int G, int P, int radius, int use_void,
+                       int32_t* region, int32_t* n_gt, int32_t* n_fg, int32_t* match, void* stream) {
+  clear_sticky_error();
+  if (T < 1 || H < 1 || W < 1 || G < 1 || P < 1 || radius < 1 || (use_void != 0 && use_void != 1)) {   // (beyond the kernel's sizes: "not covered")
+    set_error("univs_davis_counts: bad arguments T=%d H=%d W=%d G=%d P=%d radius=%d use_void=%d", T, H, W, G, P, radius, use_void);
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  if (!gt || !pred || !region || !n_gt || !n_fg || !match) {
+    set_error("univs_davis_counts: NULL data pointer");
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  return not_covered("univs_davis_counts",
+                     davis_counts(gt, pred, T, H, W, G, P, radius, use_void, region, n_gt, n_fg, match, static_cast<hipStream_t>(stream)),
+                     "G, P <= 32, radius <= 36, T H W < 2^31");
 }
 
 int univs_window_attention_image_f32(const float* qkv, const float* qkv_bias, const float* bias,
