@@ -7,7 +7,6 @@ import pytest
 import torch
 
 from tests import vps_eval_cases as C
-from univs_amd import _lib, ops
 from univs_amd.evaluation import pair_counts as pc
 from univs_amd.evaluation import vps
 
@@ -112,40 +111,3 @@ def test_wrapper_refuses_cpu_tensors_and_bad_arguments():
         pc.pair_counts_aten(gt.float(), pred, ids, ids)
     with pytest.raises(RuntimeError, match="do not cover the same"):
         pc.pair_counts_aten(gt, torch.zeros(1, 4, 5, dtype=torch.int32), ids, ids)
-
-
-class _Stub:
-    def __init__(self, code):
-        self.code, self.calls = code, []
-
-    def univs_panoptic_pair_counts(self, *args):
-        self.calls.append(args)
-        return self.code
-
-    def univs_last_error(self):
-        return b"stub"
-
-
-def test_wrapper_contract_with_the_library_stubbed(monkeypatch):
-    """What tests/test_ops_contract_cpu.py pins for the wrappers of ops.py, for this one: through `ops._call`, stream last, None on
-    ERR_NOT_IMPLEMENTED, the wrapper's name on a launch error, and no launch beyond the LDS bound."""
-    monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True), raising=False)
-    monkeypatch.setattr(ops, "_stream_ptr", lambda t: "stream")
-    gt, pred = torch.zeros(2, 4, 6, 3, dtype=torch.uint8), torch.zeros(2, 4, 6, dtype=torch.int32)
-    gi, pi = torch.arange(3), torch.arange(5)
-    lib = _Stub(_lib.OK)
-    monkeypatch.setattr(_lib, "load", lambda: lib)
-    counts, unknown = pc.panoptic_pair_counts(gt, pred, gi, pi)
-    assert tuple(counts.shape) == (2, 4, 6) and counts.dtype == torch.int32 and unknown.tolist() == [[-1, -1], [-1, -1]]
-    (args,) = lib.calls
-    assert args[-1] == "stream" and [a for a in args if isinstance(a, int) and a < 1 << 32] == [1, 0, 2, 4, 6, 3, 5]
-    lib.code = _lib.ERR_NOT_IMPLEMENTED
-    assert pc.panoptic_pair_counts(gt, pred, gi, pi) is None
-    lib.code = _lib.ERR_LAUNCH
-    with pytest.raises(_lib.UnivsHipError, match=r"^panoptic_pair_counts failed \(code -3\): stub$"):
-        pc.panoptic_pair_counts(gt, pred, gi, pi)
-    lib.code, lib.calls = _lib.OK, []
-    assert pc.panoptic_pair_counts(gt, pred, torch.arange(127), torch.arange(128)) is None      # 128 x 129 cells
-    assert pc.panoptic_pair_counts(gt, pred, torch.arange(1025), gi) is None
-    assert lib.calls == []
-    assert pc.panoptic_pair_counts(gt, pred, torch.arange(127), torch.arange(127)) is not None   # 128 x 128 = 16384 cells

@@ -16,19 +16,17 @@ The yardstick of the kernel is the ATen formulation in the same run: `kernel_fas
 
     python tools/davis_eval_bench.py [--quick] [--samples 5] [--warmup 2] [--reps 10] [--out profiles/davis_eval_bench_v1.json]
 """
-import argparse
 import json
 import os
-import statistics
 import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+import eval_bench_common as bench                         # noqa: E402
 from univs_amd.evaluation import davis                    # noqa: E402
 from univs_amd.evaluation import davis_counts as dc       # noqa: E402
 
@@ -102,86 +100,40 @@ def numpy_reference(gt, pred, G, P, r):
     return J, F
 
 
-def stats(v, digits=2):
-    return {"median": round(statistics.median(v), digits), "min": round(min(v), digits), "max": round(max(v), digits)}
-
-
 def one(T, H, W, G, P, args, dev):
     r = davis.disk_radius(H, W)
     gt, pred = scene(T, H, W, G, P)
     g, p = torch.from_numpy(gt).to(dev), torch.from_numpy(pred).to(dev)
     out = {"frames": T, "size": [H, W], "objects": G, "proposals": P, "radius": r}
-
-    def sample(fn, reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(reps):
-            fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e6 / reps
-    sides = [("kernel", lambda: dc.davis_video_counts(g, p, G, P, r, 1), args.reps), ("aten", lambda: dc.davis_counts_aten(g, p, G, P, r, 1), 1)]
-    for _ in range(args.warmup):
-        for _, fn, _ in sides:
-            fn()
-    us = {k: [] for k, _, _ in sides}
-    for _ in range(args.samples):
-        for k, fn, reps in sides:
-            us[k].append(sample(fn, reps))
-    for k in us:
-        out[f"{k}_us"] = stats(us[k])
-    a, b = sides[0][1](), sides[1][1]()
-    out["counts_equal"] = bool(all(torch.equal(x, y) for x, y in zip(a, b)))
-    out["kernel_faster_beyond_spread"] = out["kernel_us"]["max"] < out["aten_us"]["min"]
-    del a, b
+    bench.kernel_vs_aten(out, args, lambda: dc.davis_video_counts(g, p, G, P, r, 1), lambda: dc.davis_counts_aten(g, p, G, P, r, 1), "counts_equal")
     torch.cuda.empty_cache()
     with tempfile.TemporaryDirectory() as root:
         d, res = write_tree(root, gt, pred)
-        ev = []
-        for i in range(args.warmup + args.samples):
-            t0 = time.perf_counter()
-            davis.evaluate_davis_files(d, res, "unsupervised", device=dev)
-            t1 = time.perf_counter()
-            if i >= args.warmup:
-                ev.append(t1 - t0)
+        ev, _ = bench.timed(lambda: davis.evaluate_davis_files(d, res, "unsupervised", device=dev), args.warmup, args.samples)
     n = min(T, args.ref_frames)
-    ref = []
-    for _ in range(2):
-        t0 = time.perf_counter()
-        J, F = numpy_reference(gt[:n], pred[:n], G, P, r)
-        ref.append((time.perf_counter() - t0) / n)
+    ref, (J, F) = bench.timed(lambda: numpy_reference(gt[:n], pred[:n], G, P, r), 0, 2)
     ours = davis.jf_from_counts(*dc.davis_counts(g[:n].contiguous(), p[:n].contiguous(), G, P, r, 1))
     out["scores_equal"] = bool(np.array_equal(J, ours[0].transpose(1, 0, 2)) and np.array_equal(F, ours[1].transpose(1, 0, 2)))
-    out["evaluate_files_s"] = stats(ev, 3)
-    out["evaluate_files_s_per_frame"] = stats([v / T for v in ev], 4)
+    out["evaluate_files_s"] = bench.stats(ev, 3)
+    out["evaluate_files_s_per_frame"] = bench.stats([v / T for v in ev], 4)
     out["numpy_reference_frames"] = n
-    out["numpy_reference_s_per_frame"] = stats(ref, 3)
+    out["numpy_reference_s_per_frame"] = bench.stats([v / n for v in ref], 3)
     out["evaluate_faster_beyond_spread"] = out["evaluate_files_s_per_frame"]["max"] < out["numpy_reference_s_per_frame"]["min"]
     return out
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = bench.arg_parser(reps=10)
     ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--samples", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--ref_frames", type=int, default=2)
-    ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("davis_eval_bench: no GPU; a timing anywhere else says nothing")
-    dev = torch.device("cuda")
+    dev = bench.gpu_or_exit("davis_eval_bench")
     cases = [(6, 120, 214, 3, 3)] if args.quick else [(50, 480, 854, 5, 5), (50, 1080, 1920, 3, 3)]
     out = {"device": torch.cuda.get_device_name(0), "samples": args.samples, "reps": args.reps, "sequences": []}
     for c in cases:
         out["sequences"].append(one(*c, args, dev))
         print(json.dumps(out["sequences"][-1]), file=sys.stderr, flush=True)
-    line = json.dumps(out)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    bench.emit(out, args.out)
 
 
 if __name__ == "__main__":

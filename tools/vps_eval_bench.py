@@ -1,4 +1,5 @@
-"""Scoring one synthetic 720p video (20 frames, about 40 segments on each side) three ways.  Prints one JSON line:
+"""Scoring one synthetic 720p video (20 frames, about 40 segments on each side) three ways.  Prints one JSON line
+and writes it to --out:
 
   kernel_us / aten_us      the pair tables of the video (uint8 RGB on both sides, already on the device) from csrc/pair_count.hip and from
                            `pair_counts_aten` on the same GPU: median, min and max over `--samples` samples after `--warmup` untimed ones,
@@ -13,21 +14,19 @@
                            with one `==` pass per segment and STQuality's `np.unique` calls (eval_stq_vps.py:134-161).  The matching
                            itself, which costs little, is left out: a lower bound of the reference's time.
 
-    python tools/vps_eval_bench.py [--samples 5] [--warmup 2] [--reps 20] [--kernel-only]
+    python tools/vps_eval_bench.py [--samples 5] [--warmup 2] [--reps 20] [--kernel-only] [--out FILE]
 """
-import argparse
 import json
 import os
-import statistics
 import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+import eval_bench_common as bench                       # noqa: E402
 from univs_amd.evaluation import pair_counts as pc      # noqa: E402
 from univs_amd.evaluation import vps                    # noqa: E402
 
@@ -116,18 +115,11 @@ def numpy_pixel_passes(submit, truth, gt_json, pred_json):
         np.unique(yt[mask] * 2 ** 24 + yp[mask], return_counts=True)
 
 
-def stats(v, digits=2):
-    return {"median": round(statistics.median(v), digits), "min": round(min(v), digits), "max": round(max(v), digits)}
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--samples", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--reps", type=int, default=20)
+    ap = bench.arg_parser(reps=20)
     ap.add_argument("--kernel-only", action="store_true", help="skip the ATen and the host sides (the run under the kernel trace)")
     args = ap.parse_args()
-    dev = torch.device("cuda")
+    dev = bench.gpu_or_exit("vps_eval_bench")
     maps, gt_json, pred_json = scene()
     gt_ids = torch.from_numpy(vps.id_table(gt_json["annotations"][0]["annotations"])).to(dev)
     pred_ids = torch.from_numpy(vps.id_table(pred_json["annotations"][0]["annotations"])).to(dev)
@@ -135,32 +127,10 @@ def main():
     out = {"device": torch.cuda.get_device_name(0), "frames": T, "size": [H, W], "ids": [int(gt_ids.numel()), int(pred_ids.numel())],
            "samples": args.samples, "reps": args.reps}
 
-    def sample(fn, reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(reps):
-            fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e6 / reps
-
     def table_times(g, p, gt_ids, pred_ids, out):
-        sides = [("kernel", lambda: pc.panoptic_pair_counts(g, p, gt_ids, pred_ids), args.reps)]
-        if not args.kernel_only:
-            sides.append(("aten", lambda: pc.pair_counts_aten(g, p, gt_ids, pred_ids, with_unknown=True), 1))
-        for _ in range(args.warmup):
-            for _, fn, _ in sides:
-                fn()
-        us = {k: [] for k, _, _ in sides}
-        for _ in range(args.samples):
-            for k, fn, reps in sides:
-                us[k].append(sample(fn, reps))
-        for k in us:
-            out[f"{k}_us"] = stats(us[k])
-        out["kernel_GBps"] = round(6 * T * H * W / (out["kernel_us"]["median"] * 1e-6) / 1e9, 1)
-        if not args.kernel_only:
-            a, b = sides[0][1](), sides[1][1]()
-            out["tables_equal"] = bool(torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]))
-            out["kernel_faster_beyond_spread"] = out["kernel_us"]["max"] < out["aten_us"]["min"]
+        bench.kernel_vs_aten(out, args, lambda: pc.panoptic_pair_counts(g, p, gt_ids, pred_ids),
+                             None if args.kernel_only else lambda: pc.pair_counts_aten(g, p, gt_ids, pred_ids, with_unknown=True),
+                             "tables_equal", 6 * T * H * W)
     out["algorithmic_bytes"] = 6 * T * H * W
     table_times(g, p, gt_ids, pred_ids, out)
     big_maps, big_gt, big_pred = scene(1, BIG_SEGS)
@@ -170,21 +140,13 @@ def main():
     if not args.kernel_only:
         with tempfile.TemporaryDirectory() as root:
             submit, truth, gt_file = write_tree(root, maps, gt_json, pred_json)
-            ev, ref = [], []
-            for i in range(args.warmup + args.samples):
-                t0 = time.perf_counter()
-                vps.evaluate_vps_files(submit, truth, gt_file, device=dev, output_dir=os.path.join(root, "scores"))
-                t1 = time.perf_counter()
-                if i >= args.warmup:
-                    ev.append(t1 - t0)
-            for _ in range(2):
-                t0 = time.perf_counter()
-                numpy_pixel_passes(submit, truth, gt_json, pred_json)
-                ref.append(time.perf_counter() - t0)
-        out["evaluate_files_s"] = stats(ev, 3)
-        out["numpy_pixel_passes_s"] = stats(ref, 3)
+            ev, _ = bench.timed(lambda: vps.evaluate_vps_files(submit, truth, gt_file, device=dev, output_dir=os.path.join(root, "scores")),
+                                args.warmup, args.samples)
+            ref, _ = bench.timed(lambda: numpy_pixel_passes(submit, truth, gt_json, pred_json), 0, 2)
+        out["evaluate_files_s"] = bench.stats(ev, 3)
+        out["numpy_pixel_passes_s"] = bench.stats(ref, 3)
         out["evaluate_faster_beyond_spread"] = out["evaluate_files_s"]["max"] < out["numpy_pixel_passes_s"]["min"]
-    print(json.dumps(out))
+    bench.emit(out, args.out)
 
 
 if __name__ == "__main__":

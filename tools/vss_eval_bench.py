@@ -14,19 +14,16 @@ one JSON line and writes it to --out:
 
     python tools/vss_eval_bench.py [--quick] [--samples 5] [--warmup 2] [--reps 20] [--out profiles/vss_eval_bench_v1.json]
 """
-import argparse
-import json
 import os
-import statistics
 import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+import eval_bench_common as bench                       # noqa: E402
 from univs_amd.evaluation import vss                    # noqa: E402
 from univs_amd.evaluation import vss_counts as vc       # noqa: E402
 
@@ -102,71 +99,27 @@ def numpy_reference(submit, data):
     return scores
 
 
-def stats(v, digits=2):
-    return {"median": round(statistics.median(v), digits), "min": round(min(v), digits), "max": round(max(v), digits)}
-
-
 def main():
-    ap = argparse.ArgumentParser()
+    ap = bench.arg_parser(reps=20)
     ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--samples", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("vss_eval_bench: no GPU; a timing anywhere else says nothing")
+    dev = bench.gpu_or_exit("vss_eval_bench")
     T, H, W = (20, 120, 213) if args.quick else (60, 480, 853)
-    dev = torch.device("cuda")
     gt, pred = scene(T, H, W)
     g, p = torch.from_numpy(gt).to(dev), torch.from_numpy(pred).to(dev)
     out = {"device": torch.cuda.get_device_name(0), "frames": T, "size": [H, W], "num_classes": C, "samples": args.samples, "reps": args.reps,
            "algorithmic_bytes": 2 * T * H * W}
-
-    def sample(fn, reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(reps):
-            fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e6 / reps
-    sides = [("kernel", lambda: vc.vss_video_counts(g, p, C), args.reps), ("aten", lambda: vc.vss_counts_aten(g, p, C), 1)]
-    for _ in range(args.warmup):
-        for _, fn, _ in sides:
-            fn()
-    us = {k: [] for k, _, _ in sides}
-    for _ in range(args.samples):
-        for k, fn, reps in sides:
-            us[k].append(sample(fn, reps))
-    for k in us:
-        out[f"{k}_us"] = stats(us[k])
-    out["kernel_GBps"] = round(2 * T * H * W / (out["kernel_us"]["median"] * 1e-6) / 1e9, 1)
-    a, b = sides[0][1](), sides[1][1]()
-    out["counts_equal"] = bool(all(torch.equal(x, y) for x, y in zip(a, b)))
-    out["kernel_faster_beyond_spread"] = out["kernel_us"]["max"] < out["aten_us"]["min"]
+    bench.kernel_vs_aten(out, args, lambda: vc.vss_video_counts(g, p, C), lambda: vc.vss_counts_aten(g, p, C), "counts_equal", 2 * T * H * W)
     with tempfile.TemporaryDirectory() as root:
         submit, data = write_tree(root, gt, pred)
-        ev, ref = [], []
-        for i in range(args.warmup + args.samples):
-            t0 = time.perf_counter()
-            score = vss.evaluate_vss_files(submit, data, "val.txt", C, dev, output_dir=os.path.join(root, "scores"))
-            t1 = time.perf_counter()
-            if i >= args.warmup:
-                ev.append(t1 - t0)
-        for _ in range(2):
-            t0 = time.perf_counter()
-            theirs = numpy_reference(submit, data)
-            ref.append(time.perf_counter() - t0)
+        ev, score = bench.timed(lambda: vss.evaluate_vss_files(submit, data, "val.txt", C, dev, output_dir=os.path.join(root, "scores")),
+                                args.warmup, args.samples)
+        ref, theirs = bench.timed(lambda: numpy_reference(submit, data), 0, 2)
     out["scores_equal"] = bool(np.array_equal(theirs[0], score["confusion"]) and theirs[1] == score["VC8"] and theirs[2] == score["VC16"])
-    out["evaluate_files_s"] = stats(ev, 3)
-    out["numpy_reference_s"] = stats(ref, 3)
+    out["evaluate_files_s"] = bench.stats(ev, 3)
+    out["numpy_reference_s"] = bench.stats(ref, 3)
     out["evaluate_faster_beyond_spread"] = out["evaluate_files_s"]["max"] < out["numpy_reference_s"]["min"]
-    line = json.dumps(out)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    bench.emit(out, args.out)
 
 
 if __name__ == "__main__":

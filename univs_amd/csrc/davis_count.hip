@@ -32,7 +32,7 @@
 // 2 (G + P)) bytes, spans and flags 4 (r + 9).  r = 8 (480p), G = P = 5: 13.6 + 25.6 + 8 + 0.4 KB = 48 KB, three workgroups per CU;
 // r = 18 (1080p): 20.8 + 40 + 8 KB = 69 KB, two; r = 36 (4K) with G = P = 32: 38.4 + 74 + 8 + 13 KB = 134 KB of the 160 KB, one
 // (arithmetic, not measured occupancies).  DV_R_MAX = 36 is the radius of a 4K frame; 37 would still fit, nothing calls for it.
-#include "mask_post.h"
+#include "count_core.h"
 
 namespace univs {
 
@@ -91,12 +91,6 @@ __device__ __forceinline__ unsigned dv_bits_at(const unsigned char* q, int EW, i
     if (se != c) b |= dv_bit(c) | dv_bit(se);
   }
   return b;
-}
-
-__device__ __forceinline__ unsigned wave_or(unsigned v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v |= (unsigned)__shfl_xor((int)v, m, 64);
-  return v;
 }
 
 __global__ __launch_bounds__(256) void davis_count_kernel(const unsigned char* __restrict__ gt, const unsigned char* __restrict__ pred,
@@ -264,10 +258,8 @@ int davis_counts(const unsigned char* gt, const unsigned char* pred, int T, int 
   if (G > DV_MAX_OBJ || P > DV_MAX_OBJ || radius > DV_R_MAX || hw >= (1LL << 31) || hw * T >= (1LL << 31)) return UNIVS_ERR_NOT_IMPLEMENTED;
   const int tiles_x = (W + DV_TILE - 1) / DV_TILE, tiles_y = (H + DV_TILE - 1) / DV_TILE;
   const size_t lds = (size_t)davis_lds(radius, G, P).total * sizeof(int);
-  auto k = &davis_count_kernel;
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k, dim3((unsigned)(tiles_x * tiles_y * T)), dim3(256), lds, st, gt, pred, T, H, W, G, P, radius, use_void, tiles_x,
-                     tiles_y, region, n_gt, n_fg, match);
+  launch_lds(&davis_count_kernel, dim3((unsigned)(tiles_x * tiles_y * T)), lds, st, gt, pred, T, H, W, G, P, radius, use_void, tiles_x, tiles_y,
+             region, n_gt, n_fg, match);
   return check_launch("davis_counts");
 }
 

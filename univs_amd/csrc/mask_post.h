@@ -149,7 +149,7 @@ __device__ __forceinline__ float prob_at(const float* plane, int w, const OutTap
 // ---- the LDS histogram [K][3] = {mask_area, original_area, both} of the panoptic kernels --------------------------------------------
 // Accumulated in LDS over the tiles a workgroup walks, it reaches global memory once per workgroup.  All three are called by every
 // thread of a 256-thread workgroup.
-// (the _n forms: a histogram of n cells of any layout -- pair_count.hip's [G + 1][P + 1])
+// (the _n forms: a histogram of n cells of any layout -- the count kernels behind count_core.h)
 __device__ __forceinline__ void hist_zero_n(int* hist, int n) {
   for (int i = threadIdx.x; i < n; i += 256) hist[i] = 0;
   __syncthreads();

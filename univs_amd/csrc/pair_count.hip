@@ -10,8 +10,8 @@
 // pixels: whole dwords of the RGB rows (12 bytes = 3 dwords, shifted by the row segment's byte alignment), never byte loads.  It maps
 // an id by binary search in LDS and keeps the last (id, index) of each side in registers: panoptic maps are long runs, so most pixels
 // skip the search.  When the whole wave holds one pair, one lane adds 256; otherwise a lane adds each of its runs with one LDS atomic.
-// The histogram reaches global memory once per workgroup (mask_post.h: hist_flush_n).
-#include "mask_post.h"
+// (count_core.h: hist_add4).  The histogram reaches global memory once per workgroup (mask_post.h: hist_flush_n).
+#include "count_core.h"
 
 namespace univs {
 
@@ -113,22 +113,7 @@ __global__ __launch_bounds__(256) void pair_count_kernel(const unsigned char* __
         cell[j] = gi * (P + 1) + pi;
       }
     }
-    const bool one = cell[0] == cell[1] && cell[1] == cell[2] && cell[2] == cell[3];
-    const int lead = __builtin_amdgcn_readfirstlane(cell[0]);
-    if (__ballot(one && cell[0] == lead) == ~0ull) {              // the whole wave holds one pair
-      if ((threadIdx.x & 63) == 0 && lead >= 0) atomicAdd(&hist[lead], 256);
-    } else {                                                      // one LDS atomic per run of the lane's four pixels
-      int run = 1;
-#pragma unroll
-      for (int j = 1; j <= 4; ++j) {
-        if (j < 4 && cell[j] == cell[j - 1]) {
-          ++run;
-        } else {
-          if (cell[j - 1] >= 0) atomicAdd(&hist[cell[j - 1]], run);
-          run = 1;
-        }
-      }
-    }
+    hist_add4(hist, cell);
   }
   hist_flush_n(hist, cells, counts + (long long)t * cells);
   g_unknown = wave_max(g_unknown);
@@ -150,10 +135,8 @@ static void launch_pair_count(const void* gt, const void* pred, int T, int H, in
   const unsigned char* p = static_cast<const unsigned char*>(pred);
   const unsigned char* g_end = g + ((px * (GRGB ? 3 : 4) + 3) & ~3LL);
   const unsigned char* p_end = p + ((px * (PRGB ? 3 : 4) + 3) & ~3LL);
-  auto k = &pair_count_kernel<GRGB, PRGB>;
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k, dim3((unsigned)segs, (unsigned)T), dim3(256), lds, st, g, p, g_end, p_end, H, W, rps, gt_ids, G, pred_ids, P, counts,
-                     first_unknown);
+  launch_lds(&pair_count_kernel<GRGB, PRGB>, dim3((unsigned)segs, (unsigned)T), lds, st, g, p, g_end, p_end, H, W, rps, gt_ids, G, pred_ids, P,
+             counts, first_unknown);
 }
 
 int panoptic_pair_counts(const void* gt, int gt_rgb, const void* pred, int pred_rgb, int T, int H, int W, const int* gt_ids, int G,

@@ -17,12 +17,12 @@
 // A workgroup of 256 threads strides over tiles of 1024 pixel positions and walks the T frames of each; a lane owns four consecutive
 // pixels: one dword of each map per frame (two when the frame's base is not dword-aligned: H W need not be a multiple of 4), never a
 // byte load, and the next frame's dwords are in flight while this one is counted.  The window counts are summed over the wave before
-// one lane adds them in LDS; the confusion cells go to the LDS histogram as in pair_count.hip (one atomic per wave that holds one cell,
-// else one per run of a lane's four pixels).  Both reach global memory once per workgroup.
+// one lane adds them in LDS; the confusion cells go to the LDS histogram through count_core.h's hist_add4 (one atomic per wave that holds
+// one cell, else one per run of a lane's four pixels).  Both reach global memory once per workgroup.
 //
 // LDS: C C <= 16384 cells = 64 KB (the bound of pair_count.hip's PAIR_MAX_CELLS) + T <= 1024 window records of 4 ints = 16 KB: 80 KB,
 // so two workgroups fit the 160 KB of a gfx950 CU (arithmetic, not a measured occupancy).
-#include "mask_post.h"
+#include "count_core.h"
 
 namespace univs {
 
@@ -111,22 +111,7 @@ __global__ __launch_bounds__(256) void vss_count_kernel(const unsigned char* __r
           if (c16 >> 16) atomicAdd(&win[4 * (t - 15) + 3], c16 >> 16);
         }
       }
-      const bool one = cell[0] == cell[1] && cell[1] == cell[2] && cell[2] == cell[3];
-      const int lead = __builtin_amdgcn_readfirstlane(cell[0]);
-      if (__ballot(one && cell[0] == lead) == ~0ull) {            // the whole wave holds one cell
-        if ((threadIdx.x & 63) == 0 && lead >= 0) atomicAdd(&hist[lead], 256);
-      } else {                                                    // one LDS atomic per run of the lane's four pixels
-        int run = 1;
-#pragma unroll
-        for (int j = 1; j <= 4; ++j) {
-          if (j < 4 && cell[j] == cell[j - 1]) {
-            ++run;
-          } else {
-            if (cell[j - 1] >= 0) atomicAdd(&hist[cell[j - 1]], run);
-            run = 1;
-          }
-        }
-      }
+      hist_add4(hist, cell);
     }
   }
   hist_flush_n(hist, cells, confusion);
@@ -147,10 +132,7 @@ int vss_video_counts(const unsigned char* gt, const unsigned char* pred, int T, 
   const int end = (int)((px + 3) & ~3LL);
   const int tiles = ((HW + 3) / 4 + 255) / 256;
   const size_t lds = ((size_t)C * C + 4 * (size_t)T) * sizeof(int);
-  auto k = &vss_count_kernel;
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k, dim3((unsigned)std::min(tiles, VSS_MAX_BLOCKS)), dim3(256), lds, st, gt, pred, end, T, HW, C, confusion, windows,
-                     overflow);
+  launch_lds(&vss_count_kernel, dim3((unsigned)std::min(tiles, VSS_MAX_BLOCKS)), lds, st, gt, pred, end, T, HW, C, confusion, windows, overflow);
   return check_launch("vss_video_counts");
 }
 

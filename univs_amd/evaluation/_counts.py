@@ -1,0 +1,66 @@
+"""What the three count wrappers (pair_counts.py, vss_counts.py, davis_counts.py) and their drivers share.  A wrapper is
+
+    admit(name, gt, pred, check, ...)     CPU refusal, then the module's own argument check, then the device mismatch: in this order
+    its coverage bound -> None            the module's own (csrc/*_count.hip's), before anything is allocated
+    launch(name, "univs_...", gt, outputs, ...)
+
+and its module's `*_counts` is `kernel_else_aten`.  The kernels are csrc/pair_count.hip, vss_count.hip and davis_count.hip over
+csrc/count_core.h; the contract of all three wrappers is pinned in tests/test_eval_counts_contract_cpu.py.
+"""
+import numpy as np
+import torch
+
+from .. import _lib, ops
+
+
+def check_uint8_pair(name, gt, pred):
+    """gt and pred are uint8 and cover the same non-empty [T, H, W]."""
+    for side, x in (("gt", gt), ("pred", pred)):
+        if x.dtype != torch.uint8 or x.dim() != 3:
+            raise RuntimeError(f"{name}: {side} must be uint8 [T, H, W], got {x.dtype} {tuple(x.shape)}")
+    if tuple(gt.shape) != tuple(pred.shape) or 0 in gt.shape:
+        raise RuntimeError(f"{name}: gt {tuple(gt.shape)} and pred {tuple(pred.shape)} do not cover the same non-empty [T, H, W]")
+
+
+def admit(name, gt, pred, check, *args):
+    """The prologue of a kernel wrapper: CPU tensors raise as in every wrapper of ops.py, then `check(name, gt, pred, *args)` (whose
+    result is returned), then two devices raise."""
+    for side, t in (("gt", gt), ("pred", pred)):
+        if not t.is_cuda:
+            raise ops._cpu_refusal(name, f"{side} on {t.device}")
+    r = check(name, gt, pred, *args)
+    if pred.device != gt.device:
+        raise RuntimeError(f"{name}: gt on {gt.device}, pred on {pred.device}")
+    return r
+
+
+def launch(name, fn, anchor, outputs, *args):
+    """`fn` of the library (by name: looked up at call time) on `args`, then the pointers of the freshly allocated `outputs`, on
+    `anchor`'s device and current stream: `outputs`, or None where the kernel does not cover the call."""
+    ok = ops._call(name, getattr(_lib.load(), fn), anchor, *args, *(ops._ptr(o) for o in outputs))
+    return outputs if ok else None
+
+
+def kernel_else_aten(kernel, aten, gt, pred, *args):
+    """The kernel on GPU tensors where it covers the call, else the ATen formulation."""
+    if gt.is_cuda and pred.is_cuda:
+        r = kernel(gt, pred, *args)
+        if r is not None:
+            return r
+    return aten(gt, pred, *args)
+
+
+# ---- the drivers (vss.py, davis.py) -------------------------------------------------------------------------------------------------
+def read_png(path):
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.array(im)
+
+
+def pick_device(device, like=None):
+    """`device` when it is given, else the device of the GPU tensor `like`, else the GPU when there is one."""
+    if device is not None:
+        return torch.device(device)
+    if like is not None and like.is_cuda:
+        return like.device
+    return torch.device("cuda" if torch.cuda.is_available() else "cpu")

@@ -30,6 +30,7 @@ import warnings
 import numpy as np
 import torch
 
+from ._counts import pick_device as _device, read_png as _read
 from .davis_counts import davis_counts
 
 SUBSET_OPTIONS = ("train", "val", "test-dev", "test-challenge")
@@ -83,12 +84,6 @@ def db_statistics(per_frame_values):
 # ------------------------------------------------------------------------------------------------------------------------------------
 # the DAVIS tree
 # ------------------------------------------------------------------------------------------------------------------------------------
-def _read(path):
-    from PIL import Image
-    with Image.open(path) as im:
-        return np.array(im)
-
-
 def _paths(davis_root, task, subset, resolution):
     if subset not in SUBSET_OPTIONS:
         raise ValueError(f"Subset should be in {list(SUBSET_OPTIONS)}")
@@ -165,12 +160,6 @@ def read_results(res_path, seq, frame_ids):
 # ------------------------------------------------------------------------------------------------------------------------------------
 # scoring
 # ------------------------------------------------------------------------------------------------------------------------------------
-def _device(device):
-    if device is not None:
-        return torch.device(device)
-    return torch.device("cuda" if torch.cuda.is_available() else "cpu")
-
-
 def sequence_tables(gt, pred, task, metrics=("J", "F"), device=None, bound_th=0.008):
     """(j, f), float64 [G, T'] each: the per-frame series of the gt objects of one sequence, as `_evaluate_semisupervised` /
     `_evaluate_unsupervised` return them (vos_davis_evaluation.py:198-239).  gt uint8 [T, H, W] raw (with its 255s, all frames), pred

@@ -18,18 +18,15 @@ gt's 255 is never an object.  All three return int32 tensors
 """
 import torch
 
-from .. import _lib, ops
+from .. import ops
+from . import _counts
 
 MAX_OBJECTS = 32      # csrc/davis_count.hip: DV_MAX_OBJ, one bit per object
 R_MAX = 36            # DV_R_MAX: the halo in LDS (the radius of a 4K frame)
 
 
 def _check(name, gt, pred, G, P, radius):
-    for side, x in (("gt", gt), ("pred", pred)):
-        if x.dtype != torch.uint8 or x.dim() != 3:
-            raise RuntimeError(f"{name}: {side} must be uint8 [T, H, W], got {x.dtype} {tuple(x.shape)}")
-    if tuple(gt.shape) != tuple(pred.shape) or 0 in gt.shape:
-        raise RuntimeError(f"{name}: gt {tuple(gt.shape)} and pred {tuple(pred.shape)} do not cover the same non-empty [T, H, W]")
+    _counts.check_uint8_pair(name, gt, pred)
     if int(G) < 1 or int(P) < 1 or int(G) > 254 or int(P) > 255:
         raise RuntimeError(f"{name}: object counts G={G} P={P}")
     if int(radius) != radius or int(radius) < 1:
@@ -46,21 +43,14 @@ def davis_video_counts(gt, pred, G, P, radius, use_void):
     cover the call (G or P > 32, radius > R_MAX, T H W >= 2^31): the caller keeps `davis_counts_aten`.  CPU tensors raise, as in every
     wrapper of ops.py."""
     name = "davis_video_counts"
-    for side, t in (("gt", gt), ("pred", pred)):
-        if not t.is_cuda:
-            raise ops._cpu_refusal(name, f"{side} on {t.device}")
-    _check(name, gt, pred, G, P, radius)
-    if pred.device != gt.device:
-        raise RuntimeError(f"{name}: gt on {gt.device}, pred on {pred.device}")
+    _counts.admit(name, gt, pred, _check, G, P, radius)
     T, H, W = (int(v) for v in gt.shape)
     G, P, radius = int(G), int(P), int(radius)
     if G > MAX_OBJECTS or P > MAX_OBJECTS or radius > R_MAX or T * H * W >= 2 ** 31:
         return None
     gt, pred = gt.contiguous(), pred.contiguous()
-    out = _outputs(G, P, T, gt.device)
-    ok = ops._call(name, _lib.load().univs_davis_counts, gt, ops._ptr(gt), ops._ptr(pred), T, H, W, G, P, radius, 1 if use_void else 0,
-                   *(ops._ptr(o) for o in out))
-    return out if ok else None
+    return _counts.launch(name, "univs_davis_counts", gt, _outputs(G, P, T, gt.device), ops._ptr(gt), ops._ptr(pred), T, H, W, G, P, radius,
+                          1 if use_void else 0)
 
 
 def disk(radius, device=None):
@@ -121,8 +111,4 @@ def davis_counts_aten(gt, pred, G, P, radius, use_void):
 
 def davis_counts(gt, pred, G, P, radius, use_void):
     """(region, n_gt, n_fg, match): the kernel on GPU tensors where it covers the call, else the ATen formulation."""
-    if gt.is_cuda and pred.is_cuda:
-        r = davis_video_counts(gt, pred, G, P, radius, use_void)
-        if r is not None:
-            return r
-    return davis_counts_aten(gt, pred, G, P, radius, use_void)
+    return _counts.kernel_else_aten(davis_video_counts, davis_counts_aten, gt, pred, G, P, radius, use_void)

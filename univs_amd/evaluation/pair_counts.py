@@ -9,12 +9,13 @@ A map is uint8 [T, H, W, 3] (the decoded panoptic PNG, id = R + 256 G + 65536 B)
 tables are ascending and unique.  Row G / column P of a table collects the ids that are not listed; first_unknown [T, 2] names the
 largest such id of each frame's ground truth / prediction (-1: none that is >= 0).
 
-The wrapper lives here and not in ops.py: it is the one launch outside the model's forward pass, and its contract is pinned with
-the rest of this module in tests/test_vps_eval_cpu.py.
+The wrapper lives here and not in ops.py: its launch is outside the model's forward pass.  Prologue, launch and dispatch are _counts.py's,
+shared with vss_counts.py and davis_counts.py; the contract of the three is pinned in tests/test_eval_counts_contract_cpu.py.
 """
 import torch
 
-from .. import _lib, ops
+from .. import ops
+from . import _counts
 
 MAX_IDS = 1024        # csrc/pair_count.hip: PAIR_MAX_IDS
 MAX_CELLS = 16384     # PAIR_MAX_CELLS: (G + 1)(P + 1), the LDS histogram
@@ -42,12 +43,7 @@ def panoptic_pair_counts(gt, pred, gt_ids, pred_ids):
     None where the kernel does not cover the call (G or P > 1024, (G + 1)(P + 1) > 16384, T > 65535): the caller keeps
     `pair_counts_aten`.  CPU tensors raise, as in every wrapper of ops.py."""
     name = "panoptic_pair_counts"
-    for side, t in (("gt", gt), ("pred", pred)):
-        if not t.is_cuda:
-            raise ops._cpu_refusal(name, f"{side} on {t.device}")
-    g_rgb, p_rgb = _check(name, gt, pred, gt_ids, pred_ids)
-    if pred.device != gt.device:
-        raise RuntimeError(f"{name}: gt on {gt.device}, pred on {pred.device}")
+    g_rgb, p_rgb = _counts.admit(name, gt, pred, _check, gt_ids, pred_ids)
     T, H, W = (int(v) for v in gt.shape[:3])
     G, P = int(gt_ids.numel()), int(pred_ids.numel())
     if G > MAX_IDS or P > MAX_IDS or (G + 1) * (P + 1) > MAX_CELLS or T > 65535 or H * W >= 2 ** 31:
@@ -57,9 +53,8 @@ def panoptic_pair_counts(gt, pred, gt_ids, pred_ids):
     pi = pred_ids.to(device=gt.device, dtype=torch.int32).contiguous()
     counts = torch.zeros((T, G + 1, P + 1), dtype=torch.int32, device=gt.device)
     unknown = torch.full((T, 2), -1, dtype=torch.int32, device=gt.device)
-    ok = ops._call(name, _lib.load().univs_panoptic_pair_counts, gt, ops._ptr(gt), int(g_rgb), ops._ptr(pred), int(p_rgb), T, H, W,
-                   ops._ptr(gi), G, ops._ptr(pi), P, ops._ptr(counts), ops._ptr(unknown))
-    return (counts, unknown) if ok else None
+    return _counts.launch(name, "univs_panoptic_pair_counts", gt, (counts, unknown), ops._ptr(gt), int(g_rgb), ops._ptr(pred), int(p_rgb),
+                          T, H, W, ops._ptr(gi), G, ops._ptr(pi), P)
 
 
 def _flat_ids(x, rgb):
@@ -97,8 +92,4 @@ def pair_counts_aten(gt, pred, gt_ids, pred_ids, with_unknown=False):
 
 def pair_counts(gt, pred, gt_ids, pred_ids):
     """(counts, first_unknown): the kernel on GPU tensors where it covers the call, else the ATen formulation."""
-    if gt.is_cuda and pred.is_cuda:
-        r = panoptic_pair_counts(gt, pred, gt_ids, pred_ids)
-        if r is not None:
-            return r
-    return pair_counts_aten(gt, pred, gt_ids, pred_ids, with_unknown=True)
+    return _counts.kernel_else_aten(panoptic_pair_counts, lambda *a: pair_counts_aten(*a, with_unknown=True), gt, pred, gt_ids, pred_ids)

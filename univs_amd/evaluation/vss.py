@@ -25,6 +25,7 @@ import warnings
 import numpy as np
 import torch
 
+from ._counts import pick_device as _device, read_png as _read
 from .vss_counts import CLIP_NUMS, vss_counts
 
 
@@ -98,14 +99,6 @@ def score_counts(per_video_counts, split_name, output_dir=None, num_classes=124)
 # ------------------------------------------------------------------------------------------------------------------------------------
 # counts of a video, and the file-level entry points
 # ------------------------------------------------------------------------------------------------------------------------------------
-def _device(device, like=None):
-    if device is not None:
-        return torch.device(device)
-    if like is not None and like.is_cuda:
-        return like.device
-    return torch.device("cuda" if torch.cuda.is_available() else "cpu")
-
-
 def _count(gt, pred, num_classes, device):
     """numpy / torch uint8 [T, H, W] stacks -> (confusion, windows) as int64 numpy; the reference's ValueError on the overflow flag."""
     g = torch.as_tensor(gt).to(device)
@@ -115,12 +108,6 @@ def _count(gt, pred, num_classes, device):
     if over >= 0:
         raise ValueError(f"cannot reshape array of size {over + 1} into shape ({num_classes},{num_classes})")
     return confusion.cpu().numpy().astype(np.int64), windows.cpu().numpy().astype(np.int64)
-
-
-def _read(path):
-    from PIL import Image
-    with Image.open(path) as im:
-        return np.array(im)
 
 
 def read_split(data_dir, split_file):

@@ -16,7 +16,8 @@ PNGs.  The ground truth is mapped as the reference's `map_category_id` does (0 -
 """
 import torch
 
-from .. import _lib, ops
+from .. import ops
+from . import _counts
 
 MAX_CELLS = 16384     # csrc/vss_count.hip: VSS_MAX_CELLS, C C (the LDS histogram)
 MAX_FRAMES = 1024     # VSS_MAX_FRAMES: the window records in LDS
@@ -24,11 +25,7 @@ CLIP_NUMS = (8, 16)
 
 
 def _check(name, gt, pred, num_classes):
-    for side, x in (("gt", gt), ("pred", pred)):
-        if x.dtype != torch.uint8 or x.dim() != 3:
-            raise RuntimeError(f"{name}: {side} must be uint8 [T, H, W], got {x.dtype} {tuple(x.shape)}")
-    if tuple(gt.shape) != tuple(pred.shape) or 0 in gt.shape:
-        raise RuntimeError(f"{name}: gt {tuple(gt.shape)} and pred {tuple(pred.shape)} do not cover the same non-empty [T, H, W]")
+    _counts.check_uint8_pair(name, gt, pred)
     if int(num_classes) < 1:
         raise RuntimeError(f"{name}: num_classes {num_classes}")
 
@@ -38,12 +35,7 @@ def vss_video_counts(gt, pred, num_classes):
     cover the call (C C > 16384, T > 1024, T H W >= 2^31 - 4): the caller keeps `vss_counts_aten`.  CPU tensors raise, as in every
     wrapper of ops.py."""
     name = "vss_video_counts"
-    for side, t in (("gt", gt), ("pred", pred)):
-        if not t.is_cuda:
-            raise ops._cpu_refusal(name, f"{side} on {t.device}")
-    _check(name, gt, pred, num_classes)
-    if pred.device != gt.device:
-        raise RuntimeError(f"{name}: gt on {gt.device}, pred on {pred.device}")
+    _counts.admit(name, gt, pred, _check, num_classes)
     T, H, W = (int(v) for v in gt.shape)
     C = int(num_classes)
     if C * C > MAX_CELLS or T > MAX_FRAMES or T * H * W >= 2 ** 31 - 4:
@@ -52,9 +44,7 @@ def vss_video_counts(gt, pred, num_classes):
     confusion = torch.zeros((C, C), dtype=torch.int32, device=gt.device)
     windows = torch.zeros((T, 2, 2), dtype=torch.int32, device=gt.device)
     overflow = torch.full((1,), -1, dtype=torch.int32, device=gt.device)
-    ok = ops._call(name, _lib.load().univs_vss_video_counts, gt, ops._ptr(gt), ops._ptr(pred), T, H, W, C, ops._ptr(confusion),
-                   ops._ptr(windows), ops._ptr(overflow))
-    return (confusion, windows, overflow) if ok else None
+    return _counts.launch(name, "univs_vss_video_counts", gt, (confusion, windows, overflow), ops._ptr(gt), ops._ptr(pred), T, H, W, C)
 
 
 def map_category_id(gt):
@@ -91,8 +81,4 @@ def vss_counts_aten(gt, pred, num_classes):
 
 def vss_counts(gt, pred, num_classes):
     """(confusion, windows, overflow): the kernel on GPU tensors where it covers the call, else the ATen formulation."""
-    if gt.is_cuda and pred.is_cuda:
-        r = vss_video_counts(gt, pred, num_classes)
-        if r is not None:
-            return r
-    return vss_counts_aten(gt, pred, num_classes)
+    return _counts.kernel_else_aten(vss_video_counts, vss_counts_aten, gt, pred, num_classes)
