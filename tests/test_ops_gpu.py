@@ -931,7 +931,12 @@ def test_linear_split_matches_torch(cuda, linear_terms, terms, M, K, N, relu, bi
                                             (14720, 192, 576, None, False), (14720, 192, 768, "gelu", False), (3680, 768, 192, None, True),
                                             (3680, 384, 1536, "gelu", False), (4099, 96, 100, "relu", False), (2500, 768, 2304, None, False),
                                             (19320, 1024, 256, None, False), (4600, 1536, 384, None, True), (4613, 3072, 768, "gelu", False),
-                                            (5000, 1024, 128, "relu", False)],
+                                            (5000, 1024, 128, "relu", False),
+                                            # the smallest shapes at which a slip of the launch plan (passes, RB, row ranges, LDS bytes) shows:
+                                            (2048, 96, 128, None, False),      # fewest rows of the resident kernel, ring of three; f16x3: RB = 8 in one pass, bf16x6: two passes of 64
+                                            (2049, 128, 520, "gelu", False),   # five passes of 104 features, one ragged row tile
+                                            (2048, 768, 132, "relu", False),   # K >= 768 goes to the pre-split entry whatever `terms`: the tiled kernel at its smallest M, a short last tile
+                                            (2048, 768, 124, None, True)],     # ... and N < 128: the streamed kernel at its smallest M, with a residual (both `terms` alike)
                          ids=lambda v: str(v))
 @pytest.mark.parametrize("terms", [6, 3], ids=["bf16x6", "f16x3"])
 def test_linear_fused_matches_torch(cuda, linear_terms, terms, M, K, N, act, res):
@@ -1542,7 +1547,8 @@ def test_transpose_last2_is_exact(cuda, shape):
             assert torch.equal(ops.transpose_last2(z), z.transpose(-2, -1).contiguous())
 
 
-@pytest.mark.parametrize("T,Cin,Cout,H,W", [(2, 256, 256, 48, 44), (1, 128, 128, 70, 64), (3, 256, 256, 17, 83), (1, 384, 256, 64, 64)], ids=str)
+@pytest.mark.parametrize("T,Cin,Cout,H,W", [(2, 256, 256, 48, 44), (1, 128, 128, 70, 64), (3, 256, 256, 17, 83), (1, 384, 256, 64, 64),
+                                            (1, 128, 16, 64, 64)], ids=str)   # exactly 4096 pixels, one 16-feature block
 def test_conv3x3_matches_torch(cuda, T, Cin, Cout, H, W):
     """ops.conv3x3 (3 x 3, stride 1, padding 1, no bias: the x-stationary GEMM with tap addressing, three fp16 products on
     weights split once per tensor) == F.conv2d to fp32 rounding, borders and ragged row tiles included."""
@@ -1563,7 +1569,8 @@ def test_conv3x3_matches_torch(cuda, T, Cin, Cout, H, W):
 
 
 @pytest.mark.parametrize("T,Cin,Cout,H,W,bias", [(2, 256, 256, 92, 160, True), (3, 96, 256, 60, 77, False), (1, 192, 256, 46, 93, True),
-                                                  (2, 384, 256, 46, 80, True), (5, 768, 256, 23, 40, True), (1, 128, 64, 70, 70, False)],
+                                                  (2, 384, 256, 46, 80, True), (5, 768, 256, 23, 40, True), (1, 128, 64, 70, 70, False),
+                                                  (1, 128, 16, 64, 64, True)],   # exactly 4096 pixels, one 16-feature block
                          ids=lambda v: str(v))
 def test_conv1x1_matches_torch(cuda, T, Cin, Cout, H, W, bias):
     """ops.conv1x1 (the streamed three-product GEMM with the centre tap alone, bias in the epilogue) == F.conv2d to fp32 rounding:

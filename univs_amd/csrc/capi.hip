@@ -152,6 +152,65 @@ static int make_levels(const int64_t* shapes, const int64_t* starts, int L, int 
   return UNIVS_OK;
 }
 
+// The W-resident launchers return 1 if launched, 0 if not covered, < 0 on error (linear_split_f32).
+static int resident_code(int rc) { return rc > 0 ? UNIVS_OK : rc == 0 ? UNIVS_ERR_NOT_IMPLEMENTED : rc; }
+
+// The Linear entries differ in `name`, in their weight pointers (`ptrs_ok`) and in what they launch: argument validation and the
+// mapping of the launcher's code in one place.  `launch` returns UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED or an error it has reported.
+template <class F>
+static int linear_entry(const char* name, long long M, int N, int K, int act, const float* residual, bool ptrs_ok, F&& launch) {
+  clear_sticky_error();
+  if (M < 0 || N < 0 || K < 1 || act < 0 || act > 2 || (act != 0 && residual)) {
+    set_error("%s: bad arguments M=%lld N=%d K=%d act=%d%s", name, M, N, K, act,
+              (act != 0 && residual) ? " (an activation and a residual exclude each other)" : "");
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  if (M == 0 || N == 0) return UNIVS_OK;
+  if (!ptrs_ok) {
+    set_error("%s: NULL data pointer", name);
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  const int rc = launch(residual ? 3 : act);
+  if (rc == UNIVS_ERR_NOT_IMPLEMENTED) set_error("%s: shape M=%lld N=%d K=%d (or alignment) is not covered", name, M, N, K);
+  return rc;
+}
+// ... and the two with the column-blocked output
+template <class F>
+static int linear_blocked_entry(const char* name, long long M, int N, int K, int rows_per_batch, int col_block, bool ptrs_ok, F&& launch) {
+  clear_sticky_error();
+  if (M < 0 || N < 1 || K < 1 || rows_per_batch < 1 || col_block < 4 || col_block % 4 != 0 || N % col_block != 0 ||
+      (M % rows_per_batch) != 0) {
+    set_error("%s: bad arguments M=%lld N=%d K=%d rows_per_batch=%d col_block=%d", name, M, N, K, rows_per_batch, col_block);
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  if (M == 0) return UNIVS_OK;
+  if (!ptrs_ok) {
+    set_error("%s: NULL data pointer", name);
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  const int rc = resident_code(launch());
+  if (rc == UNIVS_ERR_NOT_IMPLEMENTED)
+    set_error("%s: shape M=%lld N=%d K=%d (or alignment) is not covered (K == 256, M >= 2048)", name, M, N, K);
+  return rc;
+}
+// The convolution entries on the streamed kernel; `covers`: what the entry's kernel takes
+template <class F>
+static int conv_entry(const char* name, const char* covers, int T, int Cin, int Cout, int H, int W, bool ptrs_ok, F&& launch) {
+  clear_sticky_error();
+  if (T < 0 || Cin < 1 || Cout < 0 || H < 0 || W < 0) {
+    set_error("%s: bad dimensions T=%d Cin=%d Cout=%d H=%d W=%d", name, T, Cin, Cout, H, W);
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  if (T == 0 || Cout == 0 || H == 0 || W == 0) return UNIVS_OK;
+  if (!ptrs_ok) {
+    set_error("%s: NULL data pointer", name);
+    return UNIVS_ERR_INVALID_ARGUMENT;
+  }
+  const int rc = launch();
+  if (rc == UNIVS_ERR_NOT_IMPLEMENTED) set_error("%s: T=%d Cin=%d Cout=%d H=%d W=%d not covered (%s)", name, T, Cin, Cout, H, W, covers);
+  return rc;
+}
+
 }  // namespace univs
 
 using namespace univs;
@@ -208,25 +267,9 @@ int univs_msda_last_tiled_generation(void) { return g_msda_gen; }
 
 int univs_linear_fused_f32(const float* x, const float* weight, const float* bias, const float* residual, long long M, int N,
                            int K, int act, float* y, void* stream) {
-  clear_sticky_error();
-  if (M < 0 || N < 0 || K < 1 || act < 0 || act > 2 || (act != 0 && residual)) {
-    set_error("univs_linear_fused_f32: bad arguments M=%lld N=%d K=%d act=%d%s", M, N, K, act,
-              (act != 0 && residual) ? " (an activation and a residual exclude each other)" : "");
-    return UNIVS_ERR_INVALID_ARGUMENT;
-  }
-  if (M == 0 || N == 0) return UNIVS_OK;
-  if (!x || !weight || !y) {
-    set_error("univs_linear_fused_f32: NULL data pointer");
-    return UNIVS_ERR_INVALID_ARGUMENT;
-  }
-  const int epi = residual ? 3 : act;
-  const int rc = univs::linear_split_f32(x, weight, bias, residual, y, M, N, K, epi, static_cast<hipStream_t>(stream));
-  if (rc == 1) return UNIVS_OK;
-  if (rc == 0) {
-    set_error("univs_linear_fused_f32: shape M=%lld N=%d K=%d (or alignment) is not covered", M, N, K);
-    return UNIVS_ERR_NOT_IMPLEMENTED;
-  }
-  return rc;
+  return linear_entry("univs_linear_fused_f32", M, N, K, act, residual, x && weight && y, [&](int epi) {
+    return resident_code(univs::linear_split_f32(x, weight, bias, residual, y, M, N, K, epi, static_cast<hipStream_t>(stream)));
+  });
 }
 
 
@@ -246,21 +289,8 @@ int univs_presplit_weights_f32(const float* w, int N, int K, int conv, void* wp,
 
 int univs_conv1x1_presplit_f32(const float* x, const void* wp, const float* winv, const float* bias, int T, int Cin, int Cout, int H,
                                int W, float* y, void* stream) {
-  clear_sticky_error();
-  if (T < 0 || Cin < 1 || Cout < 0 || H < 0 || W < 0) {
-    set_error("univs_conv1x1_presplit_f32: bad dimensions T=%d Cin=%d Cout=%d H=%d W=%d", T, Cin, Cout, H, W);
-    return UNIVS_ERR_INVALID_ARGUMENT;
-  }
-  if (T == 0 || Cout == 0 || H == 0 || W == 0) return UNIVS_OK;
-  if (!x || !wp || !winv || !y) {
-    set_error("univs_conv1x1_presplit_f32: NULL data pointer");
-    return UNIVS_ERR_INVALID_ARGUMENT;
-  }
-  const int rc = univs::conv1x1_f16x3_f32(x, wp, winv, bias, y, T, Cin, Cout, H, W, static_cast<hipStream_t>(stream));
-  if (rc == UNIVS_ERR_NOT_IMPLEMENTED)
-    set_error("univs_conv1x1_presplit_f32: T=%d Cin=%d Cout=%d H=%d W=%d not covered (Cin %% 96 or %% 128, Cout %% 16, >= 4096 pixels)", T,
-              Cin, Cout, H, W);
-  return rc;
+  return conv_entry("univs_conv1x1_presplit_f32", "Cin % 96 or % 128, Cout % 16, >= 4096 pixels", T, Cin, Cout, H, W, x && wp && winv && y,
+                    [&] { return univs::conv1x1_f16x3_f32(x, wp, winv, bias, y, T, Cin, Cout, H, W, static_cast<hipStream_t>(stream)); });
 }
 
 long long univs_cross_attention_workspace(int L, int S, int N, int H) {
@@ -374,109 +404,44 @@ int univs_small_mlp_presplit_f32(const float* x, int stages, const void* const* 
 
 int univs_linear_presplit_f32(const float* x, const void* wp, const float* winv, const float* bias, const float* residual,
                               long long M, int N, int K, int act, float* y, void* stream) {
-  clear_sticky_error();
-  if (M < 0 || N < 0 || K < 1 || act < 0 || act > 2 || (act != 0 && residual)) {
-    set_error("univs_linear_presplit_f32: bad arguments M=%lld N=%d K=%d act=%d%s", M, N, K, act,
-              (act != 0 && residual) ? " (an activation and a residual exclude each other)" : "");
-    return UNIVS_ERR_INVALID_ARGUMENT;
-  }
-  if (M == 0 || N == 0) return UNIVS_OK;
-  if (!x || !wp || !winv || !y) {
-    set_error("univs_linear_presplit_f32: NULL data pointer");
-    return UNIVS_ERR_INVALID_ARGUMENT;
-  }
   // the two-dimensional tiling where it applies (gemm_f16x3_tile.hip; UnivsConfig.linear_ablate == 6 switches it off: A / B), else the
   // row-range x pass kernel -- bit-identical results
-  int rc = UNIVS_ERR_NOT_IMPLEMENTED;
-  if (config().linear_ablate != 6)
-    rc = univs::linear_f16x3_tile_f32(x, wp, winv, bias, residual, y, M, N, K, residual ? 3 : act, static_cast<hipStream_t>(stream));
-  if (rc == UNIVS_ERR_NOT_IMPLEMENTED)
-    rc = univs::linear_f16x3_stream_f32(x, wp, winv, bias, residual, y, M, N, K, residual ? 3 : act, static_cast<hipStream_t>(stream));
-  if (rc == UNIVS_ERR_NOT_IMPLEMENTED) set_error("univs_linear_presplit_f32: shape M=%lld N=%d K=%d (or alignment) is not covered", M, N, K);
-  return rc;
+  return linear_entry("univs_linear_presplit_f32", M, N, K, act, residual, x && wp && winv && y, [&](int epi) {
+    int rc = UNIVS_ERR_NOT_IMPLEMENTED;
+    if (config().linear_ablate != 6)
+      rc = univs::linear_f16x3_tile_f32(x, wp, winv, bias, residual, y, M, N, K, epi, static_cast<hipStream_t>(stream));
+    if (rc == UNIVS_ERR_NOT_IMPLEMENTED)
+      rc = univs::linear_f16x3_stream_f32(x, wp, winv, bias, residual, y, M, N, K, epi, static_cast<hipStream_t>(stream));
+    return rc;
+  });
 }
 
 int univs_linear_resident_presplit_f32(const float* x, const void* wp, const float* winv, const float* bias, const float* residual,
                                        long long M, int N, int K, int act, float* y, void* stream) {
-  clear_sticky_error();
-  if (M < 0 || N < 0 || K < 1 || act < 0 || act > 2 || (act != 0 && residual)) {
-    set_error("univs_linear_resident_presplit_f32: bad arguments M=%lld N=%d K=%d act=%d%s", M, N, K, act,
-              (act != 0 && residual) ? " (an activation and a residual exclude each other)" : "");
-    return UNIVS_ERR_INVALID_ARGUMENT;
-  }
-  if (M == 0 || N == 0) return UNIVS_OK;
-  if (!x || !wp || !winv || !y) {
-    set_error("univs_linear_resident_presplit_f32: NULL data pointer");
-    return UNIVS_ERR_INVALID_ARGUMENT;
-  }
-  const int rc = univs::linear_split_f32(x, static_cast<const float*>(wp), bias, residual, y, M, N, K, residual ? 3 : act,
-                                         static_cast<hipStream_t>(stream), 0, 0, winv);
-  if (rc == 1) return UNIVS_OK;
-  if (rc == 0) {
-    set_error("univs_linear_resident_presplit_f32: shape M=%lld N=%d K=%d (or alignment) is not covered", M, N, K);
-    return UNIVS_ERR_NOT_IMPLEMENTED;
-  }
-  return rc;
+  return linear_entry("univs_linear_resident_presplit_f32", M, N, K, act, residual, x && wp && winv && y, [&](int epi) {
+    return resident_code(univs::linear_split_f32(x, static_cast<const float*>(wp), bias, residual, y, M, N, K, epi,
+                                                 static_cast<hipStream_t>(stream), 0, 0, winv));
+  });
 }
 
 int univs_linear_blocked_presplit_f32(const float* x, const void* wp, const float* winv, const float* bias, long long M, int N, int K,
                                       int rows_per_batch, int col_block, float* y, void* stream) {
-  if (M < 0 || N < 1 || K < 1 || rows_per_batch < 1 || col_block < 4 || col_block % 4 != 0 || N % col_block != 0 ||
-      (M % rows_per_batch) != 0) {
-    set_error("univs_linear_blocked_presplit_f32: bad arguments M=%lld N=%d K=%d rows_per_batch=%d col_block=%d", M, N, K, rows_per_batch,
-              col_block);
-    return UNIVS_ERR_INVALID_ARGUMENT;
-  }
-  if (M == 0) return UNIVS_OK;
-  clear_sticky_error();
-  if (!x || !wp || !winv || !y) {
-    set_error("univs_linear_blocked_presplit_f32: NULL data pointer");
-    return UNIVS_ERR_INVALID_ARGUMENT;
-  }
-  const int rc = univs::linear_split_f32(x, static_cast<const float*>(wp), bias, nullptr, y, M, N, K, /*LS_EPI_BLOCKED=*/4,
-                                         static_cast<hipStream_t>(stream), rows_per_batch, col_block, winv);
-  if (rc > 0) return UNIVS_OK;
-  if (rc == 0) {
-    set_error("univs_linear_blocked_presplit_f32: shape M=%lld N=%d K=%d (or alignment) is not covered (K == 256, M >= 2048)", M, N, K);
-    return UNIVS_ERR_NOT_IMPLEMENTED;
-  }
-  return rc;
+  return linear_blocked_entry("univs_linear_blocked_presplit_f32", M, N, K, rows_per_batch, col_block, x && wp && winv && y, [&] {
+    return univs::linear_split_f32(x, static_cast<const float*>(wp), bias, nullptr, y, M, N, K, /*LS_EPI_BLOCKED=*/4,
+                                   static_cast<hipStream_t>(stream), rows_per_batch, col_block, winv);
+  });
 }
 
 int univs_conv3x3_presplit_f32(const float* x, const void* wp, const float* winv, int T, int Cin, int Cout, int H, int W,
                                float* y, void* stream) {
-  clear_sticky_error();
-  if (T < 0 || Cin < 1 || Cout < 0 || H < 0 || W < 0) {
-    set_error("univs_conv3x3_presplit_f32: bad dimensions T=%d Cin=%d Cout=%d H=%d W=%d", T, Cin, Cout, H, W);
-    return UNIVS_ERR_INVALID_ARGUMENT;
-  }
-  if (T == 0 || Cout == 0 || H == 0 || W == 0) return UNIVS_OK;
-  if (!x || !wp || !winv || !y) {
-    set_error("univs_conv3x3_presplit_f32: NULL data pointer");
-    return UNIVS_ERR_INVALID_ARGUMENT;
-  }
-  const int rc = univs::conv3x3_f16x3_f32(x, wp, winv, y, T, Cin, Cout, H, W, static_cast<hipStream_t>(stream));
-  if (rc == UNIVS_ERR_NOT_IMPLEMENTED)
-    set_error("univs_conv3x3_presplit_f32: T=%d Cin=%d Cout=%d H=%d W=%d not covered (Cin %% 128, Cout %% 16, >= 4096 pixels)", T, Cin, Cout, H, W);
-  return rc;
+  return conv_entry("univs_conv3x3_presplit_f32", "Cin % 128, Cout % 16, >= 4096 pixels", T, Cin, Cout, H, W, x && wp && winv && y,
+                    [&] { return univs::conv3x3_f16x3_f32(x, wp, winv, y, T, Cin, Cout, H, W, static_cast<hipStream_t>(stream)); });
 }
 
 int univs_conv3x3_nhwc_presplit_f32(const float* x, const void* wp, const float* winv, int T, int Cin, int Cout, int H, int W,
                                     float* y, void* stream) {
-  clear_sticky_error();
-  if (T < 0 || Cin < 1 || Cout < 0 || H < 0 || W < 0) {
-    set_error("univs_conv3x3_nhwc_presplit_f32: bad dimensions T=%d Cin=%d Cout=%d H=%d W=%d", T, Cin, Cout, H, W);
-    return UNIVS_ERR_INVALID_ARGUMENT;
-  }
-  if (T == 0 || Cout == 0 || H == 0 || W == 0) return UNIVS_OK;
-  if (!x || !wp || !winv || !y) {
-    set_error("univs_conv3x3_nhwc_presplit_f32: NULL data pointer");
-    return UNIVS_ERR_INVALID_ARGUMENT;
-  }
-  const int rc = univs::conv3x3_nhwc_f16x3_f32(x, wp, winv, y, T, Cin, Cout, H, W, static_cast<hipStream_t>(stream));
-  if (rc == UNIVS_ERR_NOT_IMPLEMENTED)
-    set_error("univs_conv3x3_nhwc_presplit_f32: T=%d Cin=%d Cout=%d H=%d W=%d not covered (Cin %% 128, Cout %% 16, >= 4096 pixels)", T, Cin, Cout, H, W);
-  return rc;
+  return conv_entry("univs_conv3x3_nhwc_presplit_f32", "Cin % 128, Cout % 16, >= 4096 pixels", T, Cin, Cout, H, W, x && wp && winv && y,
+                    [&] { return univs::conv3x3_nhwc_f16x3_f32(x, wp, winv, y, T, Cin, Cout, H, W, static_cast<hipStream_t>(stream)); });
 }
 
 int univs_patch_embed4_f32(const float* x, const float* weight, const float* bias, const float* ln_weight, const float* ln_bias, float ln_eps,
@@ -1380,26 +1345,10 @@ int univs_msda_prepare_f32(const float* proj, int row_stride, int n_off, const f
 
 int univs_linear_blocked_f32(const float* x, const float* weight, const float* bias, long long M, int N, int K,
                              int rows_per_batch, int col_block, float* y, void* stream) {
-  if (M < 0 || N < 1 || K < 1 || rows_per_batch < 1 || col_block < 4 || col_block % 4 != 0 || N % col_block != 0 ||
-      (M % rows_per_batch) != 0) {
-    set_error("univs_linear_blocked_f32: bad arguments M=%lld N=%d K=%d rows_per_batch=%d col_block=%d", M, N, K, rows_per_batch,
-              col_block);
-    return UNIVS_ERR_INVALID_ARGUMENT;
-  }
-  if (M == 0) return UNIVS_OK;
-  clear_sticky_error();
-  if (!x || !weight || !y) {
-    set_error("univs_linear_blocked_f32: NULL data pointer");
-    return UNIVS_ERR_INVALID_ARGUMENT;
-  }
-  const int rc = univs::linear_split_f32(x, weight, bias, nullptr, y, M, N, K, /*LS_EPI_BLOCKED=*/4, static_cast<hipStream_t>(stream),
-                                         rows_per_batch, col_block);
-  if (rc > 0) return UNIVS_OK;
-  if (rc == 0) {
-    set_error("univs_linear_blocked_f32: shape M=%lld N=%d K=%d (or alignment) is not covered (K == 256, M >= 2048)", M, N, K);
-    return UNIVS_ERR_NOT_IMPLEMENTED;
-  }
-  return rc;
+  return linear_blocked_entry("univs_linear_blocked_f32", M, N, K, rows_per_batch, col_block, x && weight && y, [&] {
+    return univs::linear_split_f32(x, weight, bias, nullptr, y, M, N, K, /*LS_EPI_BLOCKED=*/4, static_cast<hipStream_t>(stream),
+                                   rows_per_batch, col_block);
+  });
 }
 
 // The two head-major MSDA entry points differ in the kernel (`forward`, generation `gen`) and in what it covers (`covers`).

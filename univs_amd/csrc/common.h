@@ -4,6 +4,9 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <mutex>
+#include <vector>
+
 #include "../../include/univs_hip.h"
 
 namespace univs {
@@ -68,6 +71,28 @@ inline int check_launch(const char* what) {
     return UNIVS_ERR_LAUNCH;
   }
   return UNIVS_OK;
+}
+
+// Compute units of the current device (256 if it cannot be asked), queried once per device.
+static inline int cu_count() {
+  static std::mutex mu;
+  static std::vector<int> by_dev;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0) {
+    (void)hipGetLastError();
+    return 256;
+  }
+  std::lock_guard<std::mutex> lock(mu);
+  if ((size_t)dev >= by_dev.size()) by_dev.resize((size_t)dev + 1, 0);
+  if (by_dev[dev] == 0) {
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) {
+      (void)hipGetLastError();
+      v = 256;
+    }
+    by_dev[dev] = v;
+  }
+  return by_dev[dev];
 }
 
 }  // namespace univs

@@ -416,26 +416,13 @@ __global__ __launch_bounds__(256) void xattn_merge(const float* __restrict__ ws,
   out[((long long)q * N + n) * (H * 32) + h * 32 + c] = acc / l;
 }
 
-static int xa_cus() {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) {
-      (void)hipGetLastError();
-      v = 256;
-    }
-    n_cu = v;
-  }
-  return n_cu;
-}
-
 // segments per (batch entry, head, chunk of 128 queries): one round of the 8 waves per CU the kernel's registers allow, each wave
 // with at least three 32-key iterations (the Q fragments cost about one)
 static int xa_segments(int L, int S, int N, int H) {
   const int nit = (S + 31) / 32, nchunks = (L + 127) / 128;
   const int forced = config().xattn_segments;
   if (forced > 0) return std::min(forced, nit);
-  const long long want = std::max<long long>(1, (8LL * xa_cus()) / ((long long)N * H * nchunks));
+  const long long want = std::max<long long>(1, (8LL * cu_count()) / ((long long)N * H * nchunks));
   // (short key sequences -- the decoder's self-attention over Q' T = 500 tokens -- are latency-bound: at least 8 segments, 22.8 vs 30.3 us)
   return (int)std::max<long long>(1, std::min<long long>(want, std::max(nit / 3, std::min(nit, 8))));
 }

@@ -10,9 +10,11 @@
 // A workgroup = 8 waves = 256 rows of x (32 per wave, two MFMA column tiles) x 128 output features per pass; W streams
 // through two LDS buffers in groups of RING k-steps (64 KB each at 128 features), one barrier per group; x keeps the
 // running per-row scale of linear_f16x3.
+// Features per pass (128, or 64 for short tall-K problems), passes, row ranges and LDS bytes: plan_stream (gemm_plan.h).
 #include "common.h"
 #include "config.h"
 #include "f16x3.h"
+#include "gemm_plan.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -22,12 +24,7 @@ namespace univs {
 #ifdef UNIVS_TRACE_GEMM
 UNIVS_GT_DECL(g_gs_trace);
 #endif
-#ifndef UNIVS_GS_THREADS
-#define UNIVS_GS_THREADS 512     // (256: timing experiment `--ablate gs256` -- two 4-wave workgroups per CU where their W buffers fit)
-#endif
-constexpr int GS_THREADS = UNIVS_GS_THREADS;
-constexpr int GS_TILE_M = 32;
-enum { GS_EPI_NONE = 0, GS_EPI_RELU = 1, GS_EPI_GELU = 2, GS_EPI_RESIDUAL = 3 };   // = LS_EPI_*
+enum { GS_EPI_NONE = EPI_NONE, GS_EPI_RELU = EPI_RELU, GS_EPI_GELU = EPI_GELU, GS_EPI_RESIDUAL = EPI_RESIDUAL };
 
 // ---- W [N, K] fp32 -> Wp [(K/32) * 4 * 2][N] 16-byte units + winv [N].  conv: W is [N, Cin, 3, 3] and k = tap * Cin + ci.
 // kperm: the k-order inside a 32-wide k-step is (4 g + e, 16 + 4 g + e) for k-group g, e = 0..3 -- the order in which the
@@ -409,45 +406,15 @@ __global__ __launch_bounds__(GS_THREADS, 512 / GS_THREADS) void gemm_f16x3_strea
   UNIVS_GT_REAL(g_gs_trace, gts, 61);
 }
 
-static int gs_cus() {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) {
-      (void)hipGetLastError();
-      v = 256;
-    }
-    n_cu = v;
-  }
-  return n_cu;
-}
-
 template <int XMODE>
-static int gs_launch(const GsArgs& a0, int ring, hipStream_t st) {
+static int gs_launch(const GsArgs& a0, hipStream_t st) {
   GsArgs a = a0;
-  const UnivsConfig cfg_ = config();
-  // output features per pass: 128, or 64 for short tall-K problems with a narrow output (Swin stage-3 / stage-4 proj and fc2:
-  // few row tiles, N <= 768 <= K -- twice the passes fill the CUs; 172 -> 126 us at 18 400 x 1536 -> 384, 60 -> 43 us at
-  // 18 400 x 384 -> 384: profiles/r04_kbench_smallm_v1.txt)
-  const bool narrow = XMODE == 0 && a.N <= 768 && a.K >= a.N && a.M <= 32768;
-  const int r_cap = cfg_.linear_rows_per_pass >= 16 ? std::min(128, cfg_.linear_rows_per_pass - cfg_.linear_rows_per_pass % 16)
-                                                    : (narrow ? 64 : 128);
-  const int passes = (a.N + r_cap - 1) / r_cap;
-  int rows = (a.N + passes - 1) / passes;
-  rows = (rows + 3) & ~3;
-  if (XMODE != 0) rows = (rows + 15) & ~15;
-  const int RB = (rows + 15) / 16;
-  a.rows_per_pass = rows;
-  a.remap = cfg_.linear_ablate == 5 ? 0 : 1;
-  const long long WT = ((long long)a.M + GS_TILE_M - 1) / GS_TILE_M;
-  long long gx = std::max<long long>(1, gs_cus() / passes);
-  gx = std::min(gx, std::max<long long>(1, WT / (GS_THREADS / 64)));
-  if (gx >= 8 && (gx - gx % 8) * 10 >= gx * 9) gx -= gx % 8;     // the passes of a row range share an XCD (linear_f16x3.hip)
-  if (cfg_.linear_grid_x > 0) gx = std::min<long long>(cfg_.linear_grid_x, WT);
-  const size_t lds = (size_t)2 * ring * 8 * (16 * RB) * 16 + 8 * (size_t)(16 * RB);
-  if (GS_THREADS < 512 && cfg_.linear_grid_x <= 0 && lds * (512 / GS_THREADS) <= 156 * 1024)      // (experiment: several workgroups per CU)
-    gx = std::min<long long>(gx * (512 / GS_THREADS), std::max<long long>(1, WT / (GS_THREADS / 64)));
-  dim3 grid((unsigned)gx, (unsigned)passes), block(GS_THREADS);
+  const StreamPlan p = plan_stream(XMODE, a.M, a.N, a.K, cu_count(), config());
+  a.rows_per_pass = p.rows_per_pass;
+  a.remap = p.remap;
+  const int RB = p.RB, ring = p.ring;
+  const size_t lds = p.lds;
+  dim3 grid(p.gx, p.passes), block(GS_THREADS);
 #define UNIVS_GS(rb, rg)                                                                                          \
   do {                                                                                                            \
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16x3_stream<rb, rg, XMODE>),                   \
@@ -478,69 +445,47 @@ static int gs_launch(const GsArgs& a0, int ring, hipStream_t st) {
 int linear_f16x3_stream_f32(const float* x, const void* wp, const float* winv, const float* bias, const float* residual, float* y,
                             long long M, int N, int K, int epi, hipStream_t st) {
   if (M <= 0 || N <= 0) return UNIVS_OK;
-  const int ring = K % 128 == 0 ? 4 : K % 96 == 0 ? 3 : 0;
-  if (epi < 0 || epi > GS_EPI_RESIDUAL || (epi == GS_EPI_RESIDUAL) != (residual != nullptr) || ring == 0 || K < 96 || N % 4 != 0 ||
-      M < 2048 || M * (long long)N * 4 >= 0x7FFFFFFFLL || M * (long long)K * 4 >= 0x7FFFFFFFLL ||
-      (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(wp) & 15) || (reinterpret_cast<uintptr_t>(y) & 15) ||
-      (reinterpret_cast<uintptr_t>(residual) & 15) || (reinterpret_cast<uintptr_t>(bias) & 15) || (reinterpret_cast<uintptr_t>(winv) & 15))
+  if (!epi_consistent(epi, EPI_RESIDUAL, residual != nullptr) || !stream_linear_covered(M, N, K) ||
+      !aligned16(x, wp, y, residual, bias, winv))
     return UNIVS_ERR_NOT_IMPLEMENTED;
   GsArgs a{};
   a.X = x; a.Wp = reinterpret_cast<const u32x4*>(wp); a.winv = winv; a.bias = bias; a.Res = residual; a.Y = y;
   a.M = (int)M; a.N = N; a.K = K; a.epi = epi;
-  return gs_launch<0>(a, ring, st);
+  return gs_launch<0>(a, st);
+}
+
+// The convolutions: the same GEMM with tap addressing of x [T, Cin, H, W] (XMODE 1) or [T, H, W, Cin] (XMODE 2), y [T, Cout, H, W];
+// `taps` = 9: a 3 x 3 (stride 1, padding 1); 1: the centre tap alone = a 1 x 1 (K = Cin; w pre-split as a Linear's [Cout, Cin])
+template <int XMODE>
+static int gs_conv(const float* x, const void* wp, const float* winv, const float* bias, float* y, int T, int Cin, int Cout, int H, int W,
+                   int taps, hipStream_t st) {
+  if (T <= 0 || Cout <= 0 || H <= 0 || W <= 0) return UNIVS_OK;
+  const long long M = (long long)T * H * W;
+  if (!stream_conv_covered(M, Cin, Cout, taps) || !aligned16(x, wp, y, winv, bias)) return UNIVS_ERR_NOT_IMPLEMENTED;
+  GsArgs a{};
+  a.X = x; a.Wp = reinterpret_cast<const u32x4*>(wp); a.winv = winv; a.bias = bias; a.Res = nullptr; a.Y = y;
+  a.M = (int)M; a.N = Cout; a.K = taps * Cin; a.epi = GS_EPI_NONE;
+  a.Cin = Cin; a.Cout = Cout; a.H = H; a.Wd = W; a.HW = H * W;
+  a.tap0 = taps == 9 ? 0 : 4;
+  return gs_launch<XMODE>(a, st);
 }
 
 int conv3x3_f16x3_f32(const float* x, const void* wp, const float* winv, float* y, int T, int Cin, int Cout, int H, int W,
                       hipStream_t st) {
-  if (T <= 0 || Cout <= 0 || H <= 0 || W <= 0) return UNIVS_OK;
-  const long long M = (long long)T * H * W;
-  if (Cin % 128 != 0 || Cout % 16 != 0 || M < 4096 || M * std::max(Cin, Cout) * 4 >= 0x7FFFFFFFLL ||
-      (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(wp) & 15) || (reinterpret_cast<uintptr_t>(y) & 15) ||
-      (reinterpret_cast<uintptr_t>(winv) & 15))
-    return UNIVS_ERR_NOT_IMPLEMENTED;
-  GsArgs a{};
-  a.X = x; a.Wp = reinterpret_cast<const u32x4*>(wp); a.winv = winv; a.bias = nullptr; a.Res = nullptr; a.Y = y;
-  a.M = (int)M; a.N = Cout; a.K = 9 * Cin; a.epi = GS_EPI_NONE;
-  a.Cin = Cin; a.Cout = Cout; a.H = H; a.Wd = W; a.HW = H * W;
-  a.tap0 = 0;
-  return gs_launch<1>(a, 4, st);
+  return gs_conv<1>(x, wp, winv, nullptr, y, T, Cin, Cout, H, W, 9, st);
 }
 
-// the same convolution on a CHANNELS-LAST operand x [T, H, W, Cin] (output NCHW as above): see XMODE 2 in the kernel
+// the same convolution on a CHANNELS-LAST operand (output NCHW as above)
 int conv3x3_nhwc_f16x3_f32(const float* x, const void* wp, const float* winv, float* y, int T, int Cin, int Cout, int H, int W,
                            hipStream_t st) {
-  if (T <= 0 || Cout <= 0 || H <= 0 || W <= 0) return UNIVS_OK;
-  const long long M = (long long)T * H * W;
-  if (Cin % 128 != 0 || Cout % 16 != 0 || M < 4096 || M * std::max(Cin, Cout) * 4 >= 0x7FFFFFFFLL ||
-      (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(wp) & 15) || (reinterpret_cast<uintptr_t>(y) & 15) ||
-      (reinterpret_cast<uintptr_t>(winv) & 15))
-    return UNIVS_ERR_NOT_IMPLEMENTED;
-  GsArgs a{};
-  a.X = x; a.Wp = reinterpret_cast<const u32x4*>(wp); a.winv = winv; a.bias = nullptr; a.Res = nullptr; a.Y = y;
-  a.M = (int)M; a.N = Cout; a.K = 9 * Cin; a.epi = GS_EPI_NONE;
-  a.Cin = Cin; a.Cout = Cout; a.H = H; a.Wd = W; a.HW = H * W;
-  a.tap0 = 0;
-  return gs_launch<2>(a, 4, st);
+  return gs_conv<2>(x, wp, winv, nullptr, y, T, Cin, Cout, H, W, 9, st);
 }
 
-// y = conv2d(x, w [Cout, Cin, 1, 1], bias) on NCHW tensors: the same kernel with the centre tap alone (K = Cin; w pre-split as a
-// Linear's [Cout, Cin]).  The lateral / mask-feature / input-projection convolutions of the pixel decoder
-// (msdeformattn.py:214-232, :262-283): the library runs them as fp32 GEMMs at ~110 TF/s and adds the bias in a second pass.
+// y = conv2d(x, w [Cout, Cin, 1, 1], bias) on NCHW tensors.  The lateral / mask-feature / input-projection convolutions of the
+// pixel decoder (msdeformattn.py:214-232, :262-283): the library runs them as fp32 GEMMs at ~110 TF/s and adds the bias in a second pass.
 int conv1x1_f16x3_f32(const float* x, const void* wp, const float* winv, const float* bias, float* y, int T, int Cin, int Cout, int H,
                       int W, hipStream_t st) {
-  if (T <= 0 || Cout <= 0 || H <= 0 || W <= 0) return UNIVS_OK;
-  const long long M = (long long)T * H * W;
-  const int ring = Cin % 128 == 0 ? 4 : Cin % 96 == 0 ? 3 : 0;
-  if (ring == 0 || Cout % 16 != 0 || M < 4096 || M * std::max(Cin, Cout) * 4 >= 0x7FFFFFFFLL ||
-      (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(wp) & 15) || (reinterpret_cast<uintptr_t>(y) & 15) ||
-      (reinterpret_cast<uintptr_t>(winv) & 15) || (reinterpret_cast<uintptr_t>(bias) & 15))
-    return UNIVS_ERR_NOT_IMPLEMENTED;
-  GsArgs a{};
-  a.X = x; a.Wp = reinterpret_cast<const u32x4*>(wp); a.winv = winv; a.bias = bias; a.Res = nullptr; a.Y = y;
-  a.M = (int)M; a.N = Cout; a.K = Cin; a.epi = GS_EPI_NONE;
-  a.Cin = Cin; a.Cout = Cout; a.H = H; a.Wd = W; a.HW = H * W;
-  a.tap0 = 4;
-  return gs_launch<1>(a, ring, st);
+  return gs_conv<1>(x, wp, winv, bias, y, T, Cin, Cout, H, W, 1, st);
 }
 
 }  // namespace univs

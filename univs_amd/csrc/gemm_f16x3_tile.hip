@@ -16,17 +16,18 @@
 //   * two LDS stages, one barrier per k-step; global loads run NSLOT - 1 k-steps ahead in registers and every load of the
 //     loop is unconditional (see gemm_f16x3_stream.hip on what hipcc does to loads under branches);
 //   * the same products in the same order per (row, feature) as the other two kernels: results are bit-identical.
+// Which (CT, RB), load depth and occupancy a shape gets is the cost model of plan_tile (gemm_plan.h).
 #include "common.h"
 #include "config.h"
 #include "f16x3.h"
+#include "gemm_plan.h"
 
 #include <algorithm>
 #include <cstdlib>
 
 namespace univs {
 
-constexpr int GT_THREADS = 512;
-enum { GT_EPI_NONE = 0, GT_EPI_RELU = 1, GT_EPI_GELU = 2, GT_EPI_RESIDUAL = 3 };   // = LS_EPI_*
+enum { GT_EPI_NONE = EPI_NONE, GT_EPI_RELU = EPI_RELU, GT_EPI_GELU = EPI_GELU, GT_EPI_RESIDUAL = EPI_RESIDUAL };
 
 struct GtArgs {
   const float* X;
@@ -240,74 +241,19 @@ __global__ __launch_bounds__(GT_THREADS, OCC) void gemm_f16x3_tile(const GtArgs 
   }
 }
 
-static int gt_cus() {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) {
-      (void)hipGetLastError();
-      v = 256;
-    }
-    n_cu = v;
-  }
-  return n_cu;
-}
-
 // returns UNIVS_OK, or UNIVS_ERR_NOT_IMPLEMENTED when the shape is not covered (the caller then takes gemm_f16x3_stream)
 int linear_f16x3_tile_f32(const float* x, const void* wp, const float* winv, const float* bias, const float* residual, float* y,
                           long long M, int N, int K, int epi, hipStream_t st) {
   if (M <= 0 || N <= 0) return UNIVS_OK;
-  // k-steps in flight per workgroup (register slots of the loads): 4 where K allows -- with 2 a k-step took ~5 000 clocks at
-  // 18 400 x 1536 -> 384, one memory latency under load: 44 KB in flight per CU, against the ~100 KB the L2 -> CU stream needs
-  int nslot = K % 128 == 0 ? 4 : K % 96 == 0 ? 3 : 2;
-  const UnivsConfig cfg_ = config();
-  if (cfg_.linear_ablate >= 7 && cfg_.linear_ablate <= 9 && K % (32 * (cfg_.linear_ablate - 5)) == 0) nslot = cfg_.linear_ablate - 5;   // kernel benchmarks
-  if (epi < 0 || epi > GT_EPI_RESIDUAL || (epi == GT_EPI_RESIDUAL) != (residual != nullptr) || K % 64 != 0 || K < 384 ||
-      N % 4 != 0 || N < 128 || M < 2048 || M * (long long)N * 4 >= 0x7FFFFFFFLL || M * (long long)K * 4 >= 0x7FFFFFFFLL ||
-      (long long)K * N * 4 >= 0x7FFFFFFFLL ||
-      (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(wp) & 15) || (reinterpret_cast<uintptr_t>(y) & 15) ||
-      (reinterpret_cast<uintptr_t>(residual) & 15) || (reinterpret_cast<uintptr_t>(bias) & 15) || (reinterpret_cast<uintptr_t>(winv) & 15))
-    return UNIVS_ERR_NOT_IMPLEMENTED;
-  // tile shape: the (CT, RB) with the least estimated time.  Per k-step and workgroup: the matrix pipe (two waves per SIMD), the LDS port
-  // (fragment reads of the 8 waves + the stage writes, 128 B / clock) and the L2 -> CU stream (~14 B / clock and CU measured for this
-  // access pattern: tools/probes/row_stride.hip).  One workgroup per CU: vector / memory phase and matrix phase add up (measured:
-  // 67 + 34 us at 18 400 x 1536 -> 384 on 160 x 192 tiles); two per CU (the small tiles): the slower pipe of the pair.  Workgroups
-  // beyond the full rounds run with the CU to themselves.  (tools/gemm_tile_sweep.py measures every shape / depth.)
-  const int ncu = gt_cus();
-  int best_ct = 0, best_rb = 0, best_nf = 0, best_tf = 0, best_occ = 1;
-  double best_t = 1e300;
-  for (int ct = 3; ct <= 5; ++ct)
-    for (int rb = 2; rb <= 4; ++rb) {
-      if (cfg_.linear_grid_x >= 3 && cfg_.linear_grid_x <= 5 && ct != cfg_.linear_grid_x) continue;              // kernel benchmarks
-      if (cfg_.linear_rows_per_pass >= 128 && rb != std::min(4, cfg_.linear_rows_per_pass / 64)) continue;
-      const int nf = (N + 64 * rb - 1) / (64 * rb);
-      int tf = (N + nf - 1) / nf;
-      tf = (tf + 3) & ~3;
-      if ((tf + 63) / 64 != rb) continue;                        // (a smaller RB covers this split)
-      const int occ = ((ct == 3 && rb <= 3) || (ct == 4 && rb == 2)) ? 2 : 1;
-      const long long wgs = ((M + 32 * ct - 1) / (32 * ct)) * nf;
-      const double ks = K / 32;
-      const double mfma = 2.0 * ct * rb * 3 * 16;
-      const double ldsc = (8.0 * (2 * ct + 2 * rb) * 1024 + 2 * ct * 2048 + tf * 128) / 128.0;
-      const double mem = (32.0 * ct * 128 + tf * 128) / 14.0;
-      const double t_alone = 1.1 * ks * (std::max(ldsc, mem) + mfma) + 6000.0;    // (1.1: 101 us measured against 93 modelled)
-      const double t_full = occ == 2 ? ks * 2.0 * std::max(mfma, std::max(ldsc, mem)) + 6000.0 : t_alone;
-      const long long full = wgs / ((long long)ncu * occ), rem = wgs - full * ncu * occ;
-      const double t = full * t_full + (rem == 0 ? 0.0 : rem > ncu ? t_full : t_alone);
-      if (t < best_t) { best_t = t; best_ct = ct; best_rb = rb; best_nf = nf; best_tf = tf; best_occ = (occ == 2 && wgs > ncu) ? 2 : 1; }
-    }
-  if (best_ct == 0) return UNIVS_ERR_NOT_IMPLEMENTED;
-  if (best_ct == 5 && best_rb == 4 && nslot == 4) nslot = K % 96 == 0 ? 3 : 2;                                    // (registers)
-  // (two workgroups per CU only where there are more workgroups than CUs; otherwise the same tile with the deeper load pipeline:
-  //  4 600 x 3072 -> 768 on 128 x 128 tiles, 216 workgroups: 95 us with 3-4 k-steps in flight, 105 with 2)
-  if (best_occ == 2) nslot = 2;                                                                                    // (128 registers)
+  if (!epi_consistent(epi, EPI_RESIDUAL, residual != nullptr) || !aligned16(x, wp, y, residual, bias, winv)) return UNIVS_ERR_NOT_IMPLEMENTED;
+  const TilePlan p = plan_tile(M, N, K, cu_count(), config());   // tile shape, load depth and occupancy: the cost model of gemm_plan.h
+  if (!p.covered) return UNIVS_ERR_NOT_IMPLEMENTED;
   GtArgs a{};
   a.X = x; a.Wp = reinterpret_cast<const u32x4*>(wp); a.winv = winv; a.bias = bias; a.Res = residual; a.Y = y;
-  a.M = (int)M; a.N = N; a.K = K; a.epi = epi; a.tf = best_tf; a.nf = best_nf;
-  const long long rt = (M + 32 * best_ct - 1) / (32 * best_ct);
-  const dim3 grid((unsigned)(rt * best_nf)), block(GT_THREADS);
-  const size_t lds = ((size_t)2 * (2 * best_ct * 128) + (size_t)2 * (8 * 64 * best_rb)) * 16 + (size_t)2 * 32 * best_ct * 4 +
-                     (size_t)2 * 64 * best_rb * 4;
+  a.M = (int)M; a.N = N; a.K = K; a.epi = epi; a.tf = p.tf; a.nf = p.nf;
+  const int best_ct = p.ct, best_rb = p.rb, best_occ = p.occ, nslot = p.nslot;
+  const dim3 grid(p.grid), block(GT_THREADS);
+  const size_t lds = p.lds;
 #define UNIVS_GT_K(ct, rb, ns, oc)                                                                                    \
   do {                                                                                                                \
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16x3_tile<ct, rb, ns, oc>),                        \
@@ -316,7 +262,7 @@ int linear_f16x3_tile_f32(const float* x, const void* wp, const float* winv, con
   } while (0)
 #define UNIVS_GT_RB(ct, rb)                                                        \
   do {                                                                             \
-    constexpr int oc = ((ct == 3 && rb <= 3) || (ct == 4 && rb == 2)) ? 2 : 1;     \
+    constexpr int oc = tile_occ2(ct, rb) ? 2 : 1;                                  \
     if (oc == 2 && best_occ == 2) UNIVS_GT_K(ct, rb, 2, oc);                       \
     else if (nslot == 4) UNIVS_GT_K(ct, rb, 4, 1);                                 \
     else if (nslot == 3) UNIVS_GT_K(ct, rb, 3, 1);                                 \

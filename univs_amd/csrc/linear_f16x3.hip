@@ -18,13 +18,15 @@
 //   * products accumulate in fp32 on v_mfma_f32_16x16x32_f16; Inf / NaN inputs poison their own row only (as in a GEMM):
 //     the row maximum ignores NaN (maxNum) and an infinite maximum scales the finite elements to ~0, the row's results
 //     are Inf / NaN either way.
-// Everything else is the organisation of linear_bf16x6 (linear_split.hip): W slab resident in LDS in A-fragment order
+// Everything else IN THE KERNEL is the organisation of linear_bf16x6 (linear_split.hip): W slab resident in LDS in A-fragment order
 // (4 bytes per element instead of 6: 128 output features of K = 256 per pass, N = 256 in two passes instead of three),
 // x streamed through a register ring, D[i = feature][j = row] so that a lane stores four consecutive features of one row,
 // epilogues ReLU / GELU / residual / column-blocked output.
+// What is launched -- coverage, passes, row ranges, LDS bytes -- is plan_f16x3_resident (gemm_plan.h), shared with linear_split.hip.
 #include "common.h"
 #include "config.h"
 #include "f16x3.h"
+#include "gemm_plan.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -34,11 +36,7 @@ namespace univs {
 #ifdef UNIVS_TRACE_GEMM
 UNIVS_GT_DECL(g_l3_trace);
 #endif
-constexpr int L3_THREADS = 512;   // 8 waves, two per SIMD
-constexpr int L3_TILE_M = 32;     // rows of x per wave tile (two 16-column MFMA tiles)
-constexpr int L3_MAX_RB = 8;
-constexpr int L3_WPT = 24;        // PRE: 16-byte units of the W slab per thread (the host side checks that the slab fits)
-enum { L3_EPI_NONE = 0, L3_EPI_RELU = 1, L3_EPI_GELU = 2, L3_EPI_RESIDUAL = 3, L3_EPI_BLOCKED = 4 };   // = LS_EPI_*
+enum { L3_EPI_NONE = EPI_NONE, L3_EPI_RELU = EPI_RELU, L3_EPI_GELU = EPI_GELU, L3_EPI_RESIDUAL = EPI_RESIDUAL, L3_EPI_BLOCKED = EPI_BLOCKED };
 
 // LDS: Wsp [K/32][4 k-groups][2 parts][16 RB features] 16 B | bias[R] | winv[R] | zero tail (16 x 16 B) | wmax[R]
 // PRE: W is the pre-split image of presplit_f16x3 (gemm_f16x3_stream.hip: [(K / 8) x 2 parts][N] 16-byte units, `winv_g` its
@@ -367,57 +365,23 @@ __global__ __launch_bounds__(L3_THREADS, 1) void linear_f16x3(const float* __res
   UNIVS_GT_REAL(g_l3_trace, gts, 61);
 }
 
-// returns 1 if launched, 0 if the shape is not covered, < 0 on error.  Same contract as linear_split_f32 (W-stationary part).
+// The three-product launch of linear_split_f32 (linear_split.hip), which has run the shared predicates and read the CU count:
+// returns 1 if launched, 0 if not covered, < 0 on error.
 // `winv` != nullptr: `w` is the pre-split image (univs_presplit_weights_f32, mode 0) and `winv` its inverse row scales
 int linear_f16x3_f32(const float* x, const float* w, const float* bias, const float* residual, float* y, long long M, int N,
-                     int K, int epi, hipStream_t st, int blk_rows, int blk_cols, const float* winv) {
-  if (M <= 0 || N <= 0) return 1;
-  if (epi < 0 || epi > L3_EPI_BLOCKED || (epi == L3_EPI_RESIDUAL) != (residual != nullptr)) return 0;
-  if (epi == L3_EPI_BLOCKED && (blk_rows < 1 || blk_cols < 4 || blk_cols % 4 != 0 || N % blk_cols != 0 || M % blk_rows != 0))
-    return 0;
-  const int ring = K % 128 == 0 ? 4 : K % 96 == 0 ? 3 : 0;   // register stages of x: a divisor of the k-steps
-  if (K < 96 || ring == 0 || N % 4 != 0) return 0;
-  if (M * (long long)N * 4 >= 0x7FFFFFFFLL || M * (long long)K * 4 >= 0x7FFFFFFFLL) return 0;
-  if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(w) & 15) || (reinterpret_cast<uintptr_t>(y) & 15) ||
-      (reinterpret_cast<uintptr_t>(residual) & 15) || (reinterpret_cast<uintptr_t>(bias) & 15) || (reinterpret_cast<uintptr_t>(winv) & 3))
-    return 0;
-  const long long lds_cap = 160 * 1024 - 2048;   // W slab + bias + inverse scales + zero tail + row maxima
-  int r_cap = (int)std::min<long long>(lds_cap / ((long long)K * 4 + 12), 16 * L3_MAX_RB);
-  r_cap -= r_cap % 16;                                     // the LDS image holds whole 16-feature blocks
+                     int K, int epi, hipStream_t st, int blk_rows, int blk_cols, const float* winv, int n_cu) {
   const UnivsConfig cfg_ = config();
-  if (cfg_.linear_rows_per_pass >= 16) r_cap = std::min(r_cap, cfg_.linear_rows_per_pass - cfg_.linear_rows_per_pass % 16);
-  if (r_cap < 16) return 0;
-  const int passes = (N + r_cap - 1) / r_cap;
-  int rows = (N + passes - 1) / passes;
-  rows = (rows + 3) & ~3;
-  const int RB = (rows + 15) / 16;
-  const long long WT = (M + L3_TILE_M - 1) / L3_TILE_M;
-  if (WT < 64) return 0;                                   // too few rows to amortise the staging of W
-  if (winv && ((K >> 3) * 2 + (L3_THREADS / rows) - 1) / (L3_THREADS / rows) > L3_WPT) return 0;   // (cannot happen for K <= 768: <= 20 units)
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) {
-      (void)hipGetLastError();
-      v = 256;
-    }
-    n_cu = v;
-  }
-  // one workgroup per CU over (row ranges x passes); the x extent a multiple of 8 so that the passes of one row range
-  // share an XCD (workgroups are dealt to the 8 XCDs round-robin by linear id)
-  long long gx = std::max<long long>(1, n_cu / passes);
-  gx = std::min(gx, std::max<long long>(1, WT / (2 * (L3_THREADS / 64))));
-  if (gx >= 8 && (gx - gx % 8) * 10 >= gx * 9) gx -= gx % 8;
-  if (cfg_.linear_grid_x > 0) gx = std::min<long long>(cfg_.linear_grid_x, WT);
-  const size_t lds = (size_t)K * (16 * RB) * 4 + 12 * (size_t)rows + 256 + 16;
-  dim3 grid((unsigned)gx, (unsigned)passes), block(L3_THREADS);
+  const ResidentPlan p = plan_f16x3_resident(M, N, K, winv != nullptr, n_cu, cfg_);
+  if (!p.covered || (reinterpret_cast<uintptr_t>(winv) & 3)) return 0;
+  const int RB = p.RB, ring = p.ring, rows = p.rows_per_pass;
+  const size_t lds = p.lds;
+  dim3 grid(p.gx, p.passes), block(L3_THREADS);
 #define UNIVS_L3(rb, rg, pre)                                                                                             \
   do {                                                                                                               \
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_f16x3<rb, rg, pre>),                                  \
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                 \
     hipLaunchKernelGGL((linear_f16x3<rb, rg, pre>), grid, block, lds, st, x, w, bias, residual, y, (int)M, N, K, rows, epi, \
-                       blk_rows, blk_cols, config().linear_ablate, winv);                                                                          \
+                       blk_rows, blk_cols, cfg_.linear_ablate, winv);                                                                              \
   } while (0)
 #define UNIVS_L3_RB(rb)                                    \
   case rb:                                                 \

@@ -8,8 +8,8 @@
 // terms accumulated in fp32; dropped terms <= 3 * 2^-24 per product) to the transposed operand layout of a Linear:
 //   * W (small, re-used by every row tile) is split once per workgroup into LDS in MFMA A-fragment order.  6 bytes per
 //     element: at most 106 output features of K = 256 per pass, so N = 256 / 288 run as three passes (blockIdx.y) over the
-//     same rows of x.  The grid's x extent is a multiple of 8, so the three workgroups that share a row range land on the
-//     same XCD at the same time and two of the three reads of x are L2 hits;
+//     same rows of x.  The grid's x extent is a multiple of 8 (plan_row_ranges, gemm_plan.h), so the three workgroups that share
+//     a row range land on the same XCD at the same time and two of the three reads of x are L2 hits;
 //   * x is streamed: a wave tile is 32 rows; lane (j, g) of MFMA column tile c holds row 32 * tile + 16 c + j, k = 32 ks +
 //     8 g .. + 7 -- 32 contiguous bytes, two 16-byte loads; four register stages (three k-steps in flight);
 //   * D[i = feature][j = row]: a lane ends up with four consecutive features of one row -> one 16-byte store; the bias is
@@ -19,8 +19,11 @@
 // K is a multiple of 128 (register ring of 4 k-steps) or of 96 (ring of 3: the Swin-T stage widths 96 and 192).
 // Everything about pinning the ring (sched_barrier, the opaque split mask, straight-line tile body, unconditional buffer
 // stores) is explained in mask_decode.hip / DESIGN.md "Toolchain hazards".
+// The host side (linear_split_f32) is the entry of BOTH W-resident kernels: the shared predicates once, then this file's
+// six-product plan or linear_f16x3.hip's three-product one (gemm_plan.h holds both).
 #include "common.h"
 #include "config.h"
+#include "gemm_plan.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -33,10 +36,7 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int LS_THREADS = 512;   // 8 waves, two per SIMD
-constexpr int LS_TILE_M = 32;     // rows of x per wave tile (two 16-column MFMA tiles)
-constexpr int LS_MAX_RB = 7;
-enum { LS_EPI_NONE = 0, LS_EPI_RELU = 1, LS_EPI_GELU = 2, LS_EPI_RESIDUAL = 3, LS_EPI_BLOCKED = 4 };
+enum { LS_EPI_NONE = EPI_NONE, LS_EPI_RELU = EPI_RELU, LS_EPI_GELU = EPI_GELU, LS_EPI_RESIDUAL = EPI_RESIDUAL, LS_EPI_BLOCKED = EPI_BLOCKED };
 // LS_EPI_BLOCKED: the output is stored column-blocked per batch element, Y[M / blk_rows][N / blk_cols][blk_rows][blk_cols]
 // (row m = b * blk_rows + s, feature n = c * blk_cols + i -> ((b * (N / blk_cols) + c) * blk_rows + s) * blk_cols + i): the
 // head-major operand layouts of the MSDeformAttn sampling kernel (msda_strips.hip: value in blocks of 16 channels, the
@@ -247,57 +247,26 @@ __global__ __launch_bounds__(LS_THREADS, 1) void linear_bf16x6(const float* __re
   }
 }
 
+// linear_f16x3.hip: the same launch on three fp16 products; the caller has run the shared predicates
 int linear_f16x3_f32(const float* x, const float* w, const float* bias, const float* residual, float* y, long long M, int N,
-                     int K, int epi, hipStream_t st, int blk_rows, int blk_cols, const float* winv);   // linear_f16x3.hip
+                     int K, int epi, hipStream_t st, int blk_rows, int blk_cols, const float* winv, int n_cu);
 
 // returns 1 if launched, 0 if the shape is not covered (the caller uses the library GEMM), < 0 on error
 // `winv` != nullptr: `w` is the pre-split image of univs_presplit_weights_f32 (three-product kernel only)
 int linear_split_f32(const float* x, const float* w, const float* bias, const float* residual, float* y, long long M, int N,
                      int K, int epi, hipStream_t st, int blk_rows, int blk_cols, const float* winv) {
   if (M <= 0 || N <= 0) return 1;
-  if (epi < 0 || epi > LS_EPI_BLOCKED || (epi == LS_EPI_RESIDUAL) != (residual != nullptr)) return 0;
-  if (epi == LS_EPI_BLOCKED && (K != 256 || blk_rows < 1 || blk_cols < 4 || blk_cols % 4 != 0 || N % blk_cols != 0 || M % blk_rows != 0))
+  if (!epi_consistent(epi, EPI_BLOCKED, residual != nullptr) || !resident_covered(M, N, K, epi, blk_rows, blk_cols) ||
+      !aligned16(x, w, y, residual, bias))
     return 0;
-  const int ring = K % 128 == 0 ? 4 : K % 96 == 0 ? 3 : 0;
-  if (K < 96 || ring == 0 || N % 4 != 0) return 0;
-  if (M * (long long)N * 4 >= 0x7FFFFFFFLL || M * (long long)K * 4 >= 0x7FFFFFFFLL) return 0;
-  if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(w) & 15) || (reinterpret_cast<uintptr_t>(y) & 15) ||
-      (reinterpret_cast<uintptr_t>(residual) & 15) || (reinterpret_cast<uintptr_t>(bias) & 15))
-    return 0;
-  // K >= 768: the weights are split once per tensor and streamed (gemm_f16x3_stream.hip: univs_linear_presplit_f32); this
-  // entry splits W in every workgroup and only pays while the whole K of a useful number of features fits LDS
-  if (K > 768) return 0;
-  if (config().linear_terms != 6 || winv)
-    return linear_f16x3_f32(x, w, bias, residual, y, M, N, K, epi, st, blk_rows, blk_cols, winv);   // default: three products
-  const long long lds_cap = 160 * 1024 - 2048;   // W slab + bias + the zeroed tail (see the staging loop)
-  int r_cap = (int)std::min<long long>(lds_cap / ((long long)K * 6), 16 * LS_MAX_RB);
-  r_cap -= r_cap % 4;
-  if (r_cap < 16) return 0;
-  const int passes = (N + r_cap - 1) / r_cap;
-  int rows = (N + passes - 1) / passes;
-  rows = (rows + 3) & ~3;
-  const int RB = (rows + 15) / 16;
-  const long long WT = (M + LS_TILE_M - 1) / LS_TILE_M;
-  if (WT < 64) return 0;                                   // too few rows to amortise the split of W
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) {
-      (void)hipGetLastError();
-      v = 256;
-    }
-    n_cu = v;
-  }
-  // one workgroup per CU over (row ranges x passes); the x extent a multiple of 8 so that the passes of one row range
-  // share an XCD (workgroups are dealt to the 8 XCDs round-robin by linear id)
-  long long gx = std::max<long long>(1, n_cu / passes);
-  gx = std::min(gx, std::max<long long>(1, WT / (2 * (LS_THREADS / 64))));
-  // (... unless rounding down to a multiple of 8 would idle more than a tenth of the CUs: 17 passes -> 15 row ranges,
-  // not 8; the passes of a row range then sit on different XCDs and x comes from the memory-side cache instead of L2)
-  if (gx >= 8 && (gx - gx % 8) * 10 >= gx * 9) gx -= gx % 8;
-  const size_t lds = (size_t)K * rows * 6 + 4 * (size_t)rows + 16 * 48 + 16;
-  dim3 grid((unsigned)gx, (unsigned)passes), block(LS_THREADS);
+  const int n_cu = cu_count();
+  if (!resident_six_products(config(), winv != nullptr))
+    return linear_f16x3_f32(x, w, bias, residual, y, M, N, K, epi, st, blk_rows, blk_cols, winv, n_cu);   // default: three products
+  const ResidentPlan p = plan_bf16x6_resident(M, N, K, epi, n_cu);
+  if (!p.covered) return 0;
+  const int RB = p.RB, ring = p.ring, rows = p.rows_per_pass;
+  const size_t lds = p.lds;
+  dim3 grid(p.gx, p.passes), block(LS_THREADS);
 #define UNIVS_LS(rb, ksc, rg, ep)                                                                                        \
   do {                                                                                                                   \
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_bf16x6<rb, ksc, rg, ep>),                            \
@@ -312,12 +281,10 @@ int linear_split_f32(const float* x, const float* w, const float* bias, const fl
     case LS_EPI_RESIDUAL: UNIVS_LS(rb, ksc, rg, LS_EPI_RESIDUAL); break; \
     default: UNIVS_LS(rb, ksc, rg, LS_EPI_NONE); break;             \
   }
-  // a straight-line tile body for K = 256 (MSDeformAttn), a runtime k loop for anything else (straight-line bodies for
-  // the Swin widths 96 .. 768 were measured: no gain, 80 s of compile time)
 #define UNIVS_LS_RB(rb)                                               \
   case rb:                                                            \
     if (epi == LS_EPI_BLOCKED) { UNIVS_LS(rb, 8, 4, LS_EPI_BLOCKED); } \
-    else if (K == 256) { UNIVS_LS_EPI(rb, 8, 4) }                     \
+    else if (p.ksc == 8) { UNIVS_LS_EPI(rb, 8, 4) }                   \
     else if (ring == 4) { UNIVS_LS_EPI(rb, 0, 4) }                    \
     else { UNIVS_LS_EPI(rb, 0, 3) }                                   \
     break

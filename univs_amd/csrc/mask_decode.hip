@@ -653,16 +653,7 @@ static int launch_bf16x6(const float* A, const float* B, int T, int Q, int K, lo
   const int rows = (Q + passes - 1) / passes;
   const int RB = (rows + 15) / 16;
   const long long WT = (N + 16 * CT - 1) / (16 * CT);
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) {
-      (void)hipGetLastError();
-      v = 256;
-    }
-    n_cu = v;
-  }
+  const int n_cu = cu_count();
   // one workgroup per CU over (frames x passes), as long as every wave has a tile (`wave_tiles` = 1).  Measured on the
   // attention-mask maps (T = 5, 100 rows; tools/kbench.py --only mask): 92 x 160 = 460 tiles: 51 workgroups 39.8 us, 29
   // workgroups (two tiles per wave) 44.4 us, and the round-2 rule (floor(460 / 16) = 28 workgroups of 16-17 tiles, i.e. a

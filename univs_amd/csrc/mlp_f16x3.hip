@@ -965,19 +965,6 @@ __global__ __launch_bounds__(512, 1) void mlp_f16x3_ps(const MlpArgs a) {
 }
 
 
-static int ml_cus() {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) {
-      (void)hipGetLastError();
-      v = 256;
-    }
-    n_cu = v;
-  }
-  return n_cu;
-}
-
 template <int KS1, int CT, int ACT, int NW, int ABL, bool DB = true>
 static int ml_launch1(MlpArgs a, size_t lds, int ngroups, hipStream_t st) {
   const void* fn = reinterpret_cast<const void*>(&mlp_f16x3<KS1, CT, ACT, NW, ABL, DB>);
@@ -991,7 +978,7 @@ static int ml_launch1(MlpArgs a, size_t lds, int ngroups, hipStream_t st) {
     }
     per_cu = nb;
   }
-  a.nwg = std::min(ml_cus() * per_cu, ngroups);
+  a.nwg = std::min(cu_count() * per_cu, ngroups);
   hipLaunchKernelGGL((mlp_f16x3<KS1, CT, ACT, NW, ABL, DB>), dim3((unsigned)a.nwg), dim3(64 * NW), lds, st, a);
   return check_launch("mlp_f16x3");
 }
@@ -1022,7 +1009,7 @@ static int ml_launch(const MlpArgs& a, int act, hipStream_t st) {
     const size_t lds_ps = (size_t)4 * 8 * C * 16 + (size_t)(2 * a.Hd + 6 * C) * 4;
     if (abl == 10 && lds_ps <= 160 * 1024) {
       MlpArgs b = a;
-      b.nwg = std::min(ml_cus(), ngroups);
+      b.nwg = std::min(cu_count(), ngroups);
       const void* fn = act == ML_ACT_RELU ? reinterpret_cast<const void*>(&mlp_f16x3_ps<KS1, ML_ACT_RELU>)
                                           : reinterpret_cast<const void*>(&mlp_f16x3_ps<KS1, ML_ACT_GELU>);
       (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));

@@ -145,27 +145,6 @@ static inline bool dense_levels(const LevelTable& lv, int L, int S, int* fine) {
   }
   return expect == S;
 }
-// Compute units of the current device (256 if it cannot be asked), queried once per device.
-static inline int cu_count() {
-  static std::mutex mu;
-  static std::vector<int> by_dev;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0) {
-    (void)hipGetLastError();
-    return 256;
-  }
-  std::lock_guard<std::mutex> lock(mu);
-  if ((size_t)dev >= by_dev.size()) by_dev.resize((size_t)dev + 1, 0);
-  if (by_dev[dev] == 0) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) {
-      (void)hipGetLastError();
-      v = 256;
-    }
-    by_dev[dev] = v;
-  }
-  return by_dev[dev];
-}
 
 // ---- the cache of per-geometry device tables
 template <class T>

@@ -431,15 +431,7 @@ int window_attention_image_f32(const float* qkv, const float* qkv_bias, const fl
   if (ws == 7 && hd == 32 && !v1 && (long long)B * H * W * 3 * nH * hd < 0x7FFFFFFFLL) {
     const int B_ = B * nW;
     if (B_ == 0) return UNIVS_OK;
-    static int n_cu = 0;
-    if (n_cu == 0) {
-      int dev = 0, v = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) {
-        (void)hipGetLastError();
-        v = 256;
-      }
-      n_cu = v;
-    }
+    const int n_cu = cu_count();
     const size_t lds = (size_t)(64 * WA2_BSTRIDE + WA_WAVES * 64 * WA_VSTRIDE) * sizeof(float);   // 54 KB: 2-3 workgroups per CU
     int gx = std::max(1, (3 * n_cu + nH - 1) / nH);
     gx = std::min(gx, (B_ + WA_WAVES - 1) / WA_WAVES);

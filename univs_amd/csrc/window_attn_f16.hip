@@ -432,16 +432,7 @@ int window_attention_image_f16mma(const float* qkv, const float* qkv_bias, const
   const int nW = (wi.Hp / ws) * wi.nWx;
   const int B_ = B * nW;
   if (B_ == 0) return UNIVS_OK;
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) {
-      (void)hipGetLastError();
-      v = 256;
-    }
-    n_cu = v;
-  }
+  const int n_cu = cu_count();
   const int ntok = ws * ws;
   if (terms == 3) {
     if (ntok <= 64) return launch_f16<4, false, 3>(qkv, qkv_bias, bias, shift_mask, B_, nW, nH, scale, out, wi, n_cu, st);
