@@ -24,7 +24,11 @@ def test_header_symbols_are_exported_and_bound():
     assert len(names) >= 8
     for n in names:
         assert hasattr(lib, n), f"{n} declared in include/univs_hip.h but not exported"
-    assert sorted(_lib.SIGNATURES) == names, "ctypes SIGNATURES table out of sync with the header"
+    # the binding is read from the header, so names alone would be a tautology: names AND types against the table recorded from
+    # the hand-typed binding (tests/capi_signatures.txt; tests/test_capi_contract_cpu.py)
+    from tests.test_capi_contract_cpu import signature_lines
+    recorded = open(os.path.join(ROOT, "tests", "capi_signatures.txt")).read().splitlines()
+    assert signature_lines(_lib.SIGNATURES) == recorded and [line.split()[0] for line in recorded] == names
 
 
 def test_version_and_error_paths_without_gpu():

@@ -1,10 +1,15 @@
 """ctypes binding of libunivs_hip.so (the C ABI declared in include/univs_hip.h).
 
+The header is the one statement of the ABI: `SIGNATURES` (restype / argtypes of every `univs_*` symbol) and `CONFIG_FIELDS` (the
+members of `struct UnivsConfig`) are read from its text when this module loads -- no table is kept by hand.
+tests/capi_signatures.txt pins the result.
+
 No fallback: if the shared library is missing or a symbol cannot be resolved this raises.  The
 product path never routes through `oracle/` or a CPU implementation.
 """
 import ctypes
 import os
+import re
 
 # Load order matters: PyTorch-ROCm bundles its own libamdhip64 and must bring the HIP runtime into the
 # process FIRST.  If libunivs_hip.so (linked against the system ROCm) is dlopen'ed before torch, two
@@ -20,91 +25,54 @@ ERR_INVALID_ARGUMENT = -1
 ERR_NOT_IMPLEMENTED = -2
 ERR_LAUNCH = -3
 
-_c = ctypes
-_P = _c.c_void_p
-_I = _c.c_int
+# The binding is read from the public header when this module loads: the header is the one statement of the ABI.
+HEADER_PATH = os.path.join(_HERE, "..", "include", "univs_hip.h")
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float,
+            "uint32_t": ctypes.c_uint32}
+_RETURNS = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "const char*": ctypes.c_char_p}
+_STRUCT = r"typedef struct UnivsConfig \{(.*?)\} UnivsConfig;"
 
-# name -> (restype, argtypes); must list every symbol of include/univs_hip.h (tests check this)
-SIGNATURES = {
-    "univs_version": (_c.c_char_p, []),
-    "univs_last_error": (_c.c_char_p, []),
-    "univs_msda_forward_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "univs_msda_forward_f64": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "univs_msda_backward_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
-    "univs_msda_forward_strips_f32": (_I, [_P, _P, _P, _P, _P, _c.c_longlong, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "univs_msda_forward_heads_f32": (_I, [_P, _P, _P, _P, _P, _c.c_longlong, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "univs_linear_blocked_f32": (_I, [_P, _P, _P, _c.c_longlong, _I, _I, _I, _I, _P, _P]),
-    "univs_configure": (_I, [_P]),
-    "univs_get_config": (_I, [_P]),
-    "univs_msda_set_impl": (_I, [_I]),
-    "univs_msda_last_impl": (_I, []),
-    "univs_msda_last_tiled_generation": (_I, []),
-    "univs_transpose_f32": (_I, [_P, _c.c_longlong, _I, _I, _P, _P]),
-    "univs_transpose_strided_f32": (_I, [_P, _c.c_longlong, _I, _I, _c.c_longlong, _P, _P]),
-    "univs_transpose_ex_f32": (_I, [_P, _c.c_longlong, _I, _I, _c.c_longlong, _P, _P, _c.c_longlong, _P, _P, _P]),
-    "univs_linear_fused_f32": (_I, [_P, _P, _P, _P, _c.c_longlong, _I, _I, _I, _P, _P]),
-    "univs_mask_decode_set_impl": (_I, [_I]),
-    "univs_mask_decode_last_impl": (_I, []),
-    "univs_mask_decode_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
-    "univs_mask_decode_attn_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
-    "univs_window_attention_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _c.c_float, _P, _P]),
-    "univs_msda_prepare_f32": (_I, [_P, _I, _I, _P, _c.c_longlong, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "univs_window_attention_image_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _c.c_float, _P, _P]),
-    "univs_presplit_weights_f32": (_I, [_P, _I, _I, _I, _P, _P, _P]),
-    "univs_linear_presplit_f32": (_I, [_P, _P, _P, _P, _P, _c.c_longlong, _I, _I, _I, _P, _P]),
-    "univs_conv3x3_presplit_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
-    "univs_conv3x3_nhwc_presplit_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
-    "univs_linear_resident_presplit_f32": (_I, [_P, _P, _P, _P, _P, _c.c_longlong, _I, _I, _I, _P, _P]),
-    "univs_linear_blocked_presplit_f32": (_I, [_P, _P, _P, _P, _c.c_longlong, _I, _I, _I, _I, _P, _P]),
-    "univs_conv1x1_presplit_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
-    "univs_patch_embed4_f32": (_I, [_P, _P, _P, _P, _P, _c.c_float, _I, _I, _I, _I, _P, _P]),
-    "univs_decoder_memory_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
-    "univs_cross_attention_workspace": (_c.c_longlong, [_I, _I, _I, _I]),
-    "univs_cross_attention_flagged_f32": (_I, [_P, _P, _P, _P, _P, _c.c_uint32, _I, _I, _I, _I, _I, _I, _I, _I, _c.c_float, _P, _P, _P]),
-    "univs_mask_decode_attn_deferred_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _c.c_uint32, _P]),
-    "univs_attn_mask_rows_reset": (_I, [_P, _P, _c.c_uint32, _c.c_longlong, _c.c_longlong, _P]),
-    "univs_cross_attention_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _c.c_float, _P, _P, _P]),
-    "univs_small_linear_presplit_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _c.c_float, _c.c_longlong, _I, _I, _I, _I, _I, _P, _P]),
-    "univs_small_mlp_presplit_f32": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _c.c_float, _P, _c.c_longlong, _I, _P, _P]),
-    "univs_mlp_presplit_v2_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _c.c_float, _P, _P, _c.c_float, _P, _c.c_longlong, _P,
-                                       _c.c_longlong, _I, _I, _I, _P, _P]),
-    "univs_mlp_presplit_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _c.c_float, _P, _P, _c.c_float, _P, _c.c_longlong, _P,
-                                    _c.c_longlong, _I, _I, _I, _P, _P]),
-    "univs_window_attention_image_mma": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _c.c_float, _I, _P, _P]),
-    "univs_upsample2x_add_f32": (_I, [_P, _P, _P, _P, _c.c_longlong, _I, _I, _P]),
-    "univs_group_norm_affine_f32": (_I, [_P, _P, _P, _I, _I, _c.c_longlong, _I, _c.c_float, _P, _c.c_longlong, _P, _P]),
-    "univs_bilinear_pyramid3_f32": (_I, [_P, _c.c_longlong, _I, _I, _P, _P, _P, _P]),
-    "univs_bilinear_resample_f32": (_I, [_P, _P, _P, _c.c_longlong, _I, _I, _I, _I, _P]),
-    "univs_bilinear_crop_nearest_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "univs_normalize_pad_f32": (_I, [_P, _P, _P, _c.c_longlong, _I, _I, _I, _I, _I, _P, _P]),
-    "univs_patch_merge_norm_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _c.c_float, _P, _P]),
-    "univs_layer_norm_f32": (_I, [_P, _P, _P, _P, _c.c_longlong, _I, _c.c_float, _P, _P, _P]),
-    "univs_layer_norm_add_f32": (_I, [_P, _P, _P, _P, _P, _c.c_longlong, _c.c_longlong, _I, _c.c_float, _P, _P, _P, _P]),
-    "univs_group_norm_f32": (_I, [_P, _P, _P, _I, _I, _c.c_longlong, _I, _c.c_float, _I, _P, _c.c_longlong, _P, _P]),
-    "univs_masked_softmax_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "univs_proca_attention_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _c.c_float, _P, _P]),
-    "univs_prompt_prefix_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _c.c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "univs_prompt_draw": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
-    "univs_prompt_point_pe_f32": (_I, [_P, _P, _P, _P, _c.c_float, _I, _I, _I, _P, _P]),
-    "univs_token_mean_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
-    "univs_mask_stats_f32": (_I, [_P, _c.c_longlong, _I, _I, _I, _I, _c.c_float, _c.c_float, _c.c_float, _P, _P]),
-    "univs_mask_stats_strided_f32": (_I, [_P, _c.c_longlong, _I, _c.c_longlong, _c.c_longlong, _I, _I, _I, _I, _c.c_float, _c.c_float, _c.c_float, _P, _P]),
-    "univs_prompt_tokens_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
-    "univs_image_mask_stats_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "univs_image_panoptic_ids_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
-    "univs_image_panoptic_paint_i32": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
-    "univs_image_semseg_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
-    "univs_image_instance_masks_u8": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
-    "univs_minvis_accumulate_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P]),
-    "univs_video_mask_stats_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P]),
-    "univs_video_instance_masks_u8": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P]),
-    "univs_video_panoptic_ids_i32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P]),
-    "univs_video_panoptic_counts_i32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P]),
-    "univs_video_panoptic_paint_i32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P]),
-    "univs_panoptic_pair_counts": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P]),
-    "univs_vss_video_counts": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
-    "univs_davis_counts": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
-}
+
+def strip_header(text):
+    """The header without its comments, preprocessor lines and extern "C" braces."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", text, flags=re.S)
+    return re.sub(r"^[ \t]*(#.*|extern \"C\" \{|\})[ \t]*$", "", text, flags=re.M)
+
+
+def parse_signatures(text):
+    """name -> (restype, argtypes) of every `univs_*` prototype in the header `text`.  Any pointer parameter is a c_void_p;
+    a type outside the two maps raises and names the symbol -- it is never guessed."""
+    def ctype(words, table, name):
+        t = " ".join(words).replace(" *", "*")
+        if t.endswith("*") and table is _SCALARS:
+            return ctypes.c_void_p
+        if t not in table:
+            raise TypeError(f"{name}: type {t!r} in include/univs_hip.h has no ctypes mapping")
+        return table[t]
+
+    sigs = {}
+    text = re.sub(_STRUCT, "", strip_header(text), flags=re.S)
+    for ret, name, params in re.findall(r"([\w \t*]+?)\b(univs_\w+)\s*\(([^)]*)\)\s*;", text):
+        params = [] if params.strip() == "void" else [p.replace("*", " * ").split()[:-1] for p in params.split(",")]   # [:-1]: the name
+        sigs[name] = (ctype(ret.replace("*", " * ").split(), _RETURNS, name), [ctype(p, _SCALARS, name) for p in params])
+    return sigs
+
+
+def parse_config_fields(text):
+    """The members of `struct UnivsConfig` as ctypes fields: plain ints and int arrays (`reserved[2]`)."""
+    fields = []
+    for decl in re.search(_STRUCT, strip_header(text), flags=re.S).group(1).split(";")[:-1]:
+        m = re.fullmatch(r"\s*int\s+(\w+)\s*(?:\[(\d+)\])?\s*", decl)
+        if not m:
+            raise TypeError(f"UnivsConfig: member {decl.strip()!r} in include/univs_hip.h is not an int or an int array")
+        fields.append((m.group(1), ctypes.c_int * int(m.group(2)) if m.group(2) else ctypes.c_int))
+    return fields
+
+
+with open(HEADER_PATH) as _f:
+    _HEADER = _f.read()
+SIGNATURES = parse_signatures(_HEADER)
+CONFIG_FIELDS = parse_config_fields(_HEADER)
 
 _lib = None
 

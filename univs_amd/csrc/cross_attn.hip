@@ -28,6 +28,7 @@
 //   * every wave writes (m, l, O[32]) per query for its segment; a second small kernel merges the segments
 //     (out = sum_p O_p 2^(m_p - M) / sum_p l_p 2^(m_p - M)) and stores [L, N, h d].
 #include "common.h"
+#include "launchers.h"
 #include "config.h"
 #include "f16x3.h"
 

@@ -33,6 +33,7 @@
 // r = 18 (1080p): 20.8 + 40 + 8 KB = 69 KB, two; r = 36 (4K) with G = P = 32: 38.4 + 74 + 8 + 13 KB = 134 KB of the 160 KB, one
 // (arithmetic, not measured occupancies).  DV_R_MAX = 36 is the radius of a 4K frame; 37 would still fit, nothing calls for it.
 #include "count_core.h"
+#include "launchers.h"
 
 namespace univs {
 

@@ -15,6 +15,7 @@
 #include "config.h"
 #include "f16x3.h"
 #include "gemm_plan.h"
+#include "launchers.h"
 
 #include <algorithm>
 #include <cstdlib>

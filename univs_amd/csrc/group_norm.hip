@@ -9,6 +9,7 @@
 //   pass 2: every workgroup first folds the partials of its group (<= 1024 values), then normalises its
 //           own chunk: y = (x - mean) * rstd * gamma[c] + beta[c] (biased variance, as ATen), optional ReLU.
 #include "common.h"
+#include "launchers.h"
 
 namespace univs {
 

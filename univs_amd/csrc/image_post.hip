@@ -18,6 +18,7 @@
 // (plane descriptor with V = 1, record, histogram, grids) and the image_stats / instance_masks kernels, which are the video ones with
 // other template arguments, are in mask_post.h.
 #include "mask_post.h"
+#include "launchers.h"
 
 namespace univs {
 

@@ -10,6 +10,7 @@
 // two-pass statistics (mean, then sum of squared deviations), biased variance, rstd = 1/sqrt(var + eps),
 // y = (x - mean) * rstd * gamma + beta -- the same expression order as ATen's kernel.
 #include "common.h"
+#include "launchers.h"
 
 namespace univs {
 

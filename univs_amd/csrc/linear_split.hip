@@ -24,6 +24,7 @@
 #include "common.h"
 #include "config.h"
 #include "gemm_plan.h"
+#include "launchers.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -246,10 +247,6 @@ __global__ __launch_bounds__(LS_THREADS, 1) void linear_bf16x6(const float* __re
     }
   }
 }
-
-// linear_f16x3.hip: the same launch on three fp16 products; the caller has run the shared predicates
-int linear_f16x3_f32(const float* x, const float* w, const float* bias, const float* residual, float* y, long long M, int N,
-                     int K, int epi, hipStream_t st, int blk_rows, int blk_cols, const float* winv, int n_cu);
 
 // returns 1 if launched, 0 if the shape is not covered (the caller uses the library GEMM), < 0 on error
 // `winv` != nullptr: `w` is the pre-split image of univs_presplit_weights_f32 (three-product kernel only)

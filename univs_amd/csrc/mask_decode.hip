@@ -18,6 +18,7 @@
 // scalar fp32 loop bit-for-bit -- what the 1e-3 / argmax-identical parity contract needs.
 #include "common.h"
 #include "config.h"
+#include "launchers.h"
 
 #include <algorithm>
 #include <cstdlib>

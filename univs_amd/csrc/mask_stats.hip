@@ -9,6 +9,7 @@
 // the atomics arrive in.  The record, its per-workgroup flush and the row-segment grid are shared with the other mask post-processing
 // kernels: mask_post.h.
 #include "mask_post.h"
+#include "launchers.h"
 
 namespace univs {
 

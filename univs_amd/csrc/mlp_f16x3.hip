@@ -24,6 +24,7 @@
 #include "common.h"
 #include "config.h"
 #include "f16x3.h"
+#include "launchers.h"
 
 #include <algorithm>
 #include <cstdlib>

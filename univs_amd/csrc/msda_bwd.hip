@@ -7,6 +7,7 @@
 // with corners outside the image contributing nothing (zero padding) and samples outside the band
 // (-1, H) x (-1, W) skipped, exactly like the forward (ms_deform_im2col_cuda.cuh:285-293).
 #include "msda_common.h"
+#include "launchers.h"
 
 namespace univs {
 

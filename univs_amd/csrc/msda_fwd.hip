@@ -18,6 +18,7 @@
 //   * kernel "scalar": any D / double precision, one thread per output element (KAT shapes of
 //     ops/test.py use D=2).
 #include "msda_common.h"
+#include "launchers.h"
 
 namespace univs {
 

@@ -31,6 +31,7 @@
 #include "msda_heads_geom.h"
 #include "config.h"
 #include "msda_dev.h"
+#include "launchers.h"
 
 // Timing experiments (python -m univs_amd.build --ablate heads_*; results are then WRONG): S6_ABLATE bit 0 = no gather stream
 // (LDS reads + multiply-adds), bit 1 = no row movement in the steady state (loads + LDS commits), bit 2 = no point

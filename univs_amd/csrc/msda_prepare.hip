@@ -10,6 +10,7 @@
 // Arithmetic in the reference's order: off / normalizer (IEEE division), then + reference point; softmax as
 // exp(x - max) / sum.
 #include "common.h"
+#include "launchers.h"
 
 namespace univs {
 

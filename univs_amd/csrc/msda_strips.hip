@@ -38,6 +38,7 @@
 #include "msda_strips_geom.h"
 #include "config.h"
 #include "msda_dev.h"
+#include "launchers.h"
 
 namespace univs {
 

@@ -21,6 +21,7 @@
 // Needs L >= 3 (the next item's query list is built two steps before its first sample loads).
 #include "config.h"
 #include "msda_geometry.h"
+#include "launchers.h"
 
 #ifdef UNIVS_MSDA_TRACE
 // Debug builds only (tools/msda_trace.py): per-workgroup s_memtime stamps (own array: no relocatable device code)

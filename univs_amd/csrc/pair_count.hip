@@ -12,6 +12,7 @@
 // skip the search.  When the whole wave holds one pair, one lane adds 256; otherwise a lane adds each of its runs with one LDS atomic.
 // (count_core.h: hist_add4).  The histogram reaches global memory once per workgroup (mask_post.h: hist_flush_n).
 #include "count_core.h"
+#include "launchers.h"
 
 namespace univs {
 

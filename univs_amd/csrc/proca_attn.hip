@@ -12,6 +12,7 @@
 // 16-byte loads of its key's 128 contiguous bytes; scores in LDS.  Softmax by wave reductions.  Phase 2: lane = (key parity,
 // channel): p v over half of the keys each, 128-byte coalesced rows, the two halves added by one permlane swap.
 #include "common.h"
+#include "launchers.h"
 
 namespace univs {
 

@@ -13,6 +13,7 @@
 // random stream): these kernels turn them into pixels.  Bit-exact against the ATen formulation of univs_amd/modeling/prompt_encoder.py
 // (tests/test_prompt_sampler_gpu.py), which stays the CPU path and the GPU oracle.
 #include "common.h"
+#include "launchers.h"
 
 #include <algorithm>
 

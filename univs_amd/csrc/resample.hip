@@ -15,6 +15,7 @@
 // h1p / w1p edge handling, the lambda products) so that results agree to rounding.
 #include "common.h"
 #include "resample_taps.h"
+#include "launchers.h"
 
 namespace univs {
 

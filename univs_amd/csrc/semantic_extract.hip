@@ -18,6 +18,7 @@
 // (one 128-byte line per tap pair) and the launch is small, so every plane gets its own blocks.
 #include "common.h"
 #include "resample_taps.h"
+#include "launchers.h"
 
 namespace univs {
 

@@ -19,6 +19,7 @@
 // whole rows (N == 256) -- nn.LayerNorm with exact two-pass statistics across the eight waves (two LDS exchanges).
 #include "common.h"
 #include "f16x3.h"
+#include "launchers.h"
 
 #include <algorithm>
 #include <cstdlib>

@@ -8,6 +8,7 @@
 // streaming passes.  Same formula as ATen: exp(x - max) / sum, masked entries contribute 0 (a fully
 // masked row gives NaN there and here; the caller never produces one, ...decoder_univs.py:390).
 #include "common.h"
+#include "launchers.h"
 
 namespace univs {
 

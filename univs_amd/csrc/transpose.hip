@@ -6,6 +6,7 @@
 // a permuted copy at ~0.6 TB/s (360 us for the 113-MB res2 map at 720p x 5 frames); this is the classic LDS tile
 // transpose: 64 x 64 tiles, 16-byte loads along the input's fast axis, 16-byte stores along the output's.
 #include "common.h"
+#include "launchers.h"
 
 namespace univs {
 

@@ -20,6 +20,7 @@
 // The building blocks (plane descriptor, taps of the second resize, histogram, grids) and the video_stats / video_instance_masks
 // kernels, which are the image ones with other template arguments, are in mask_post.h.
 #include "mask_post.h"
+#include "launchers.h"
 
 namespace univs {
 

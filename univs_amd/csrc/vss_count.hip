@@ -23,6 +23,7 @@
 // LDS: C C <= 16384 cells = 64 KB (the bound of pair_count.hip's PAIR_MAX_CELLS) + T <= 1024 window records of 4 ints = 16 KB: 80 KB,
 // so two workgroups fit the 160 KB of a gfx950 CU (arithmetic, not a measured occupancy).
 #include "count_core.h"
+#include "launchers.h"
 
 namespace univs {
 

@@ -20,6 +20,7 @@
 #include "common.h"
 #include "config.h"
 #include "window_attn.h"
+#include "launchers.h"
 
 #include <algorithm>
 #include <cstdlib>

@@ -28,6 +28,7 @@
 #include "config.h"
 #include "f16x3.h"
 #include "window_attn.h"
+#include "launchers.h"
 
 #include <algorithm>
 

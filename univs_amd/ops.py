@@ -311,10 +311,7 @@ def msda_forward_strips(value_hm, proj_hm, ref_points, spatial_shapes, level_sta
 # ---- settings (include/univs_hip.h: UnivsConfig) ----------------------------------------------------------------------------------------
 class UnivsConfig(ctypes.Structure):
     """include/univs_hip.h: UnivsConfig -- the library's process-wide settings (it reads no environment variable)."""
-    _fields_ = [(n, ctypes.c_int) for n in ("size", "msda_impl", "msda_strip_w", "msda_strip_h", "msda_halo", "msda_grid",
-                                            "mask_decode_impl", "mask_decode_ct", "mask_decode_ablate", "window_attn_v1",
-                                            "linear_terms", "linear_ablate", "mask_decode_chunked", "mask_decode_wave_tiles",
-                                            "linear_rows_per_pass", "linear_grid_x", "xattn_segments", "msda_sched")] + [("reserved", ctypes.c_int * 2)]
+    _fields_ = _lib.CONFIG_FIELDS      # read from the header's struct
 
 
 def get_config() -> dict:
