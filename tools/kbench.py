@@ -318,6 +318,16 @@ def main():
                     t = timeit(lambda: ops.window_attention_image(q, qb, bi, mk if shift else None, H_, W_, ws, shift, hd ** -0.5, mma=mma))
                     res[f"window12_{H_}x{W_}_shift{shift}_{mma}"] = dict(
                         ms=t * 1e3, us_per_frame=t * 1e6 / Tw, GBps=byts / t / 1e9, frac_hbm=byts / t / HBM_PEAK)
+    if args.only and "gn" in args.only:
+        # the GroupNorms of the pixel decoder (32 groups of 8 channels) at 720p x T frames: 2 reads + 1 write / 1 read of x
+        for (h, w) in ((184, 320), (92, 160), (46, 80), (23, 40)):
+            xg = (synth.normal(f"kb/gn/x/{h}", (T, 256, h, w)) * 2.0 + 0.7).to(dev)
+            gw, gb = (1.0 + 0.1 * synth.uniform("kb/gn/w", (256,))).to(dev), (0.05 * synth.uniform("kb/gn/b", (256,))).to(dev)
+            byts = xg.numel() * 4.0
+            t = timeit(lambda: ops.group_norm(xg, 32, gw, gb, 1e-5, relu=True), iters=500, warmup=20)
+            res[f"group_norm_{h}x{w}"] = dict(us=t * 1e6, GBps=3 * byts / t / 1e9, frac_hbm=3 * byts / t / HBM_PEAK)
+            t = timeit(lambda: ops.group_norm_affine(xg, 32, gw, gb, 1e-5), iters=500, warmup=20)
+            res[f"group_norm_affine_{h}x{w}"] = dict(us=t * 1e6, GBps=byts / t / 1e9, frac_hbm=byts / t / HBM_PEAK)
     if not args.only or "resample" in args.only:
         f = synth.normal("kb/f", (T, 256, 184, 320)).to(dev)
         for (h, w) in ((92, 160), (46, 80), (23, 40)):

@@ -5,9 +5,17 @@
 // convs).  At [5, 256, 184, 320] ATen runs RowwiseMoments at 1.5 TB/s plus a separate apply (+ a separate
 // ReLU): 0.55 ms per call.  Two passes are the minimum (a group = 8 x 58 880 floats does not fit on chip):
 //   pass 1: every workgroup reduces one spatial chunk of one channel plane to (sum, sum of squares) of
-//           x - shift, shift = the group's first element (keeps E[x^2] - E[x]^2 out of cancellation);
+//           x - shift, shift = gn_shift of the group;
 //   pass 2: every workgroup first folds the partials of its group (<= 1024 values), then normalises its
 //           own chunk: y = (x - mean) * rstd * gamma[c] + beta[c] (biased variance, as ATen), optional ReLU.
+// The statistics are one-pass: var = E[d^2] - E[d]^2 with d = x - shift, which loses about (shift - mean)^2 / var of fp32's
+// resolution to cancellation.  The shift is therefore the mean of 64 elements of the group, 8 runs of 8 from the middle of its
+// eighths (gn_shift): one element, whatever its value and wherever it sits (the zero-padded image corner, an activation spike),
+// moves it by 1 / 64 of its distance from the rest, a whole run by 1 / 8, and a shift within a few standard deviations of the mean
+// costs nothing measurable.  It guarantees nothing about a group in which several of the 8 runs are outliers while the bulk is not.
+// A constant group gives shift = that constant exactly, every d = 0, var = 0 and y = beta up to the rounding of bias = beta -
+// mean * scale.  The three kernels take the same shift and the same sums in the same order, so their (scale, bias) agree bit for
+// bit (tests/test_group_norm_numerics_cpu.py restates the arithmetic).
 #include "common.h"
 #include "launchers.h"
 
@@ -25,26 +33,65 @@ __device__ __forceinline__ float block_sum_256(float v, float* lds) {
   return lds[0] + lds[1] + lds[2] + lds[3];
 }
 
+// The shift of a group (its Cg planes are one contiguous run of n floats at gp): the mean of 64 of its elements, GN_RUN consecutive ones
+// from the middle of each of its 64 / GN_RUN equal parts (8 cache lines; one line per sample costs the statistics pass 8 %).  Every
+// wave loads the same 64 values (L2 hits after the group's first workgroup) and sums them with the same butterfly, so every lane of
+// every workgroup of the three kernels holds the same bits; no LDS, no barrier.  Groups shorter than the pattern repeat their last
+// element.  Two steps, so that a kernel can issue the load first and take the mean where it needs it: the round trip then hides
+// behind the kernel's other loads.
+constexpr int GN_RUN = 8;
+__device__ __forceinline__ float gn_shift_sample(const float* __restrict__ gp, long long n) {
+  const long long j = threadIdx.x & 63, part = j / GN_RUN;
+  const long long i = ((2 * part + 1) * n) / (2 * (64 / GN_RUN)) + j % GN_RUN;
+  return gp[i < n ? i : n - 1];
+}
+__device__ __forceinline__ float gn_shift(float sample) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sample += __shfl_xor(sample, o, 64);
+  return sample * (1.f / 64.f);
+}
+
 // grid: (chunks, N * C); plane = blockIdx.y
 __global__ __launch_bounds__(256) void gn_partials_kernel(const float* __restrict__ x, int C, int Cg, long long HW,
                                                           int chunks, float* __restrict__ partials) {
   __shared__ float red[4];
   const long long plane = blockIdx.y;
   const long long n = plane / C, c = plane % C, g = c / Cg;
-  const float shift = x[(n * C + g * Cg) * HW];
+  const float sample = gn_shift_sample(x + (n * C + g * Cg) * HW, Cg * HW);
   const long long per = (HW + chunks - 1) / chunks;
   const long long lo = (long long)blockIdx.x * per, hi = lo + per < HW ? lo + per : HW;
   const float* p = x + plane * HW;
   float s1 = 0.f, s2 = 0.f;
+  // in both paths the lane's first two loads go out behind the sample, before the shift is taken from it
   if ((HW & 3) == 0 && (per & 3) == 0) {
     const v4f* p4 = reinterpret_cast<const v4f*>(p);
-    for (long long i = lo / 4 + threadIdx.x; i < hi / 4; i += 256) {
-      const v4f d = p4[i] - shift;
+    const auto add = [&](v4f d) {
       s1 += (d.x + d.y) + (d.z + d.w);
       s2 += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
-    }
+    };
+    long long i = lo / 4 + threadIdx.x;
+    const long long end = hi / 4;
+    const v4f zero = {0.f, 0.f, 0.f, 0.f};
+    const v4f a = i < end ? p4[i] : zero, b = i + 256 < end ? p4[i + 256] : zero;
+    const float shift = gn_shift(sample);
+    if (i < end) add(a - shift);
+    if (i + 256 < end) add(b - shift);
+    for (i += 512; i < end; i += 256) add(p4[i] - shift);
   } else {
-    for (long long i = lo + threadIdx.x; i < hi; i += 256) {
+    long long i = lo + threadIdx.x;
+    const float a = i < hi ? p[i] : 0.f, b = i + 256 < hi ? p[i + 256] : 0.f;
+    const float shift = gn_shift(sample);
+    if (i < hi) {
+      const float d = a - shift;
+      s1 += d;
+      s2 += d * d;
+    }
+    if (i + 256 < hi) {
+      const float d = b - shift;
+      s1 += d;
+      s2 += d * d;
+    }
+    for (i += 512; i < hi; i += 256) {
       const float d = p[i] - shift;
       s1 += d;
       s2 += d * d;
@@ -66,7 +113,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
   const long long plane = blockIdx.y;
   const long long n = plane / C, c = plane % C, g = c / Cg;
   const long long g0 = n * C + g * Cg;          // first plane of the group
-  const float shift = x[g0 * HW];
+  const float sample = gn_shift_sample(x + g0 * HW, Cg * HW);   // (the mean of it below, behind the partials' loads)
   float s1 = 0.f, s2 = 0.f;
   for (int i = threadIdx.x; i < Cg * chunks; i += 256) {
     s1 += partials[(g0 * chunks + i) * 2];
@@ -77,7 +124,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
   const float inv_n = 1.f / ((float)Cg * (float)HW);
   const float m1 = s1 * inv_n;
   const float var = fmaxf(s2 * inv_n - m1 * m1, 0.f);
-  const float mean = shift + m1;
+  const float mean = gn_shift(sample) + m1;
   const float scale = gamma[c] / sqrtf(var + eps);
   const float bias = beta[c] - mean * scale;
   const long long per = (HW + chunks - 1) / chunks;
@@ -110,7 +157,7 @@ __global__ __launch_bounds__(256) void gn_affine_kernel(const float* __restrict_
   const long long plane = blockIdx.x;
   const long long n = plane / C, c = plane % C, g = c / Cg;
   const long long g0 = n * C + g * Cg;
-  const float shift = x[g0 * HW];
+  const float sample = gn_shift_sample(x + g0 * HW, Cg * HW);   // (the mean of it below, behind the partials' loads)
   float s1 = 0.f, s2 = 0.f;
   for (int i = threadIdx.x; i < Cg * chunks; i += 256) {
     s1 += partials[(g0 * chunks + i) * 2];
@@ -121,7 +168,7 @@ __global__ __launch_bounds__(256) void gn_affine_kernel(const float* __restrict_
   const float inv_n = 1.f / ((float)Cg * (float)HW);
   const float m1 = s1 * inv_n;
   const float var = fmaxf(s2 * inv_n - m1 * m1, 0.f);
-  const float mean = shift + m1;
+  const float mean = gn_shift(sample) + m1;
   const float scale = gamma[c] / sqrtf(var + eps);
   const float bias = beta[c] - mean * scale;
   if (threadIdx.x == 0) {

@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void layer_norm_f32_kernel(const float* __rest
         v[j] = (v4f){0.f, 0.f, 0.f, 0.f};
       }
     }
-    const float mean = group_sum<G>(s) * inv_c;
+    const float mean = group_sum<G>(s) / (float)C;   // a division: s * (1 / C) is not the mean of a constant row
     float q = 0.f;
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256) void patch_merge_norm_kernel(const float* __re
         s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
       }
     }
-    const float mean = group_sum<G>(s) * inv_c;
+    const float mean = group_sum<G>(s) / (float)(4 * C);   // a division: s * (1 / C) is not the mean of a constant row
     float q = 0.f;
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
