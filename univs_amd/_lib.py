@@ -1,4 +1,4 @@
-"""ctypes binding of libunivs_hip.so (the C ABI declared in include/univs_hip.h).
+"""ctypes binding of libunivs_hip.so (the C ABI declared in include/univs_hip.h and include/univs_eval_hip.h).
 
 The header is the one statement of the ABI: `SIGNATURES` (restype / argtypes of every `univs_*` symbol) and `CONFIG_FIELDS` (the
 members of `struct UnivsConfig`) are read from its text when this module loads -- no table is kept by hand.
@@ -73,6 +73,10 @@ with open(HEADER_PATH) as _f:
     _HEADER = _f.read()
 SIGNATURES = parse_signatures(_HEADER)
 CONFIG_FIELDS = parse_config_fields(_HEADER)
+# The second header (include/univs_eval_hip.h: the entries added after the first one's symbols were pinned) has a table of its own.
+EVAL_HEADER_PATH = os.path.join(_HERE, "..", "include", "univs_eval_hip.h")
+with open(EVAL_HEADER_PATH) as _f:
+    EVAL_SIGNATURES = parse_signatures(_f.read())
 
 _lib = None
 
@@ -92,7 +96,7 @@ def load():
             f"{LIB_PATH} not found: the HIP extension is mandatory (no CPU fallback). "
             "Build it with `python -m univs_amd.build`.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in (*SIGNATURES.items(), *EVAL_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing -> loud
         fn.restype = res
         fn.argtypes = args

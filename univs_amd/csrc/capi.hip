@@ -5,6 +5,7 @@
 
 #include <mutex>
 
+#include "../../include/univs_eval_hip.h"
 #include "common.h"
 #include "config.h"
 #include "launchers.h"
@@ -827,6 +828,17 @@ int univs_davis_counts(const uint8_t* gt, const uint8_t* pred, int T, int H, int
     return e.invalid("bad arguments T=%d H=%d W=%d G=%d P=%d radius=%d use_void=%d", T, H, W, G, P, radius, use_void);
   if (!gt || !pred || !region || !n_gt || !n_fg || !match) return e.null_pointer();
   return e.covered(davis_counts(gt, pred, T, H, W, G, P, radius, use_void, region, n_gt, n_fg, match, e.st), "not covered (G, P <= 32, radius <= 36, T H W < 2^31)");
+}
+
+// (include/univs_eval_hip.h)
+int univs_vis_overlap_counts(const int32_t* dt_bounds, const int32_t* dt_starts, const int32_t* gt_bounds, const int32_t* gt_ones,
+                             const int32_t* gt_starts, int D, int G, int T, int H, int W, int gt_max_bounds, int32_t* inter, void* stream) {
+  const Entry e("univs_vis_overlap_counts", stream);
+  if (D < 1 || G < 1 || T < 1 || H < 1 || W < 1 || gt_max_bounds < 0 || (long long)D * G * T >= (1LL << 31))
+    return e.invalid("bad arguments D=%d G=%d T=%d H=%d W=%d gt_max_bounds=%d (D G T < 2^31)", D, G, T, H, W, gt_max_bounds);
+  if (!dt_bounds || !dt_starts || !gt_bounds || !gt_ones || !gt_starts || !inter) return e.null_pointer();
+  return e.covered(vis_overlap_counts(dt_bounds, dt_starts, gt_bounds, gt_ones, gt_starts, D, G, T, H, W, gt_max_bounds, inter, e.st),
+                   "not covered (H W < 2^31, T <= 65535, at most 16384 boundaries per ground-truth mask: 128 KB of LDS)");
 }
 
 // The two window-attention entries on image-layout operands share their checks

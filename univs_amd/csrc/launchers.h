@@ -194,4 +194,8 @@ int vss_video_counts(const unsigned char* gt, const unsigned char* pred, int T, 
 int davis_counts(const unsigned char* gt, const unsigned char* pred, int T, int H, int W, int G, int P, int radius, int use_void,
                  int* region, int* n_gt, int* n_fg, int* match, hipStream_t st);
 
+// ---- vis_overlap.hip: returns UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the shape is not covered, or the launch's error
+int vis_overlap_counts(const int* dt_bounds, const int* dt_starts, const int* gt_bounds, const int* gt_ones, const int* gt_starts, int D,
+                       int G, int T, int H, int W, int gt_max_bounds, int* inter, hipStream_t st);
+
 }  // namespace univs

@@ -1,12 +1,20 @@
 """Scoring of the result files the inference drivers write: VIPSeg VPQ / STQ (vps.py, on the pair tables of pair_counts.py), VSPW
 mIoU / VC8 / VC16 (vss.py, on the per-video counts of vss_counts.py) and DAVIS J / F (davis.py, on the per-pair counts of
-davis_counts.py)."""
+davis_counts.py) and YouTube-VIS AP / AR (ytvis.py, on the per-video overlap counts of vis_counts.py)."""
 _DAVIS = ("DAVISEvaluator", "db_statistics", "disk_radius", "evaluate_davis_files", "jf_from_counts", "read_sequence")
-__all__ = list(_DAVIS)
+_YTVIS = ("YTVISEval", "YTVISEvaluator", "derive_coco_results", "evaluate_predictions_on_ytvis", "load_results")
+_VIS_COUNTS = ("Runs", "runs_from_rles", "vis_overlap", "vis_overlap_aten", "vis_video_overlap")
+__all__ = list(_DAVIS + _YTVIS + _VIS_COUNTS)
 
 
 def __getattr__(name):                       # on first use: `python -m univs_amd.evaluation.davis` imports this package before its module
     if name in _DAVIS:
         from . import davis
         return getattr(davis, name)
+    if name in _YTVIS:
+        from . import ytvis
+        return getattr(ytvis, name)
+    if name in _VIS_COUNTS:
+        from . import vis_counts
+        return getattr(vis_counts, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
