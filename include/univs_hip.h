@@ -160,7 +160,8 @@ typedef struct UnivsConfig {
   int linear_rows_per_pass; /* kernel benchmarks: output features per pass of the three-product Linears (a multiple of 16, <= 128;
                              0 = as many as fit: 128 for the streamed kernel, the LDS capacity for the W-resident one) */
   int linear_grid_x;      /* kernel benchmarks: workgroups along the rows of the three-product Linears (0 = by shape) */
-  int xattn_segments;     /* kernel benchmarks: key segments per (batch entry, head, query chunk) of univs_cross_attention_f32 (0 = by shape) */
+  int xattn_segments;     /* kernel benchmarks: key segments per (batch entry, head, query chunk) of univs_cross_attention_f32 (0 = by shape);
+                             + 65536 x n (n = 1 .. 7) also fixes the query blocks (of 16 queries) a wave takes; negative values count as 0 */
   int msda_sched;         /* msda_heads: 0 / 2 = the workgroups of an XCD walk adjacent tile columns in lockstep rounds (default),
                              1 = one contiguous range of the (plane, column, row) sequence per workgroup (generation 5's rule; A / B runs) */
   int reserved[2];

@@ -13,7 +13,8 @@
 // exp2 domain.  Range: as there, a wave tests its operands and applies a wave-uniform power of two only when a magnitude
 // would leave fp16's range or the whole block is tiny.
 //
-// Organisation: one WAVE per workgroup handles one (batch entry n, head h) and one segment of the keys, all (<= 128) queries:
+// Organisation: one WAVE per workgroup handles one (batch entry n, head h), one segment of the keys and one chunk of 16 NQB queries
+// (NQB query blocks per wave, 1 .. 7: a launch choice, see xa_plan):
 //   * S^T = K (Q scale)^T per 16-key block and 16-query block, so that a lane holds S[query j][keys 4 g .. 4 g + 3]: the
 //     probabilities of TWO key blocks are, as they stand, the A operand of one 16x16x32 product P V over 32 keys with the
 //     k-order (4 g + e, 16 + 4 g + e);
@@ -46,9 +47,9 @@ struct XaArgs {
   const unsigned char* mask; // [N, L, S] (non-zero = masked out) or null
   const unsigned* flags;     // [N, Lfull] or null: row (n, l) of the mask counts only where flags == gen; elsewhere every key is visible
   unsigned gen;              //   (the all-masked-row rule of ...decoder_univs.py:390, deferred: mask_decode.hip)
-  float* ws;                 // [N * H][nseg][16 NQB][34]: O[32], m, l
+  float* ws;                 // [chunk][N * H][nseg][16 NQB][34]: O[32], m, l
   float* out;                // [L, N, H * 32]
-  int L, S, N, H, nseg;      // L: queries; a workgroup (blockIdx.z = chunk) handles queries [128 chunk, 128 chunk + 128)
+  int L, S, N, H, nseg;      // L: queries; a workgroup (blockIdx.z = chunk) handles queries [16 NQB chunk, 16 NQB (chunk + 1))
   int Lfull, l0;             // rows of the mask per batch entry (= L), 0
   int ldq, ldk, ldv;         // floats between consecutive batch entries of q / k / v (>= H * 32: slices of wider projections)
   float qscale;              // scale * log2(e)
@@ -74,13 +75,24 @@ __device__ __forceinline__ void xa_wave_scale(float mx, float& s, float& inv, in
 __device__ __forceinline__ bool xa_out_of_range(float mx, float lo) {
   return __builtin_amdgcn_ballot_w64(!(mx < 32768.0f)) != 0 || __builtin_amdgcn_ballot_w64(mx >= lo) == 0;
 }
-__device__ __forceinline__ void xa_split8(const float (&x)[8], f16x8& h, f16x8& m) {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const _Float16 hh = (_Float16)x[e];
-    h[e] = hh;
-    m[e] = (_Float16)(x[e] - (float)hh);
-  }
+// Accumulator start of the scores of a lane's four keys, whose mask bytes are one dword: -inf where the byte is set, else 0 -- one
+// byte-select compare and one select per key.  (The trailing s_nop: the four registers are the C operand of a matrix instruction, and
+// hipcc pads no hazard whose producer sits inside an asm statement.)
+__device__ __forceinline__ f32x4 xa_mask_init(unsigned mw, float ninf) {
+  float c0, c1, c2, c3;
+  asm("v_cmp_ne_u32_sdwa vcc, %4, 0 src0_sel:BYTE_0 src1_sel:DWORD\n\t"
+      "v_cndmask_b32 %0, 0, %5, vcc\n\t"
+      "v_cmp_ne_u32_sdwa vcc, %4, 0 src0_sel:BYTE_1 src1_sel:DWORD\n\t"
+      "v_cndmask_b32 %1, 0, %5, vcc\n\t"
+      "v_cmp_ne_u32_sdwa vcc, %4, 0 src0_sel:BYTE_2 src1_sel:DWORD\n\t"
+      "v_cndmask_b32 %2, 0, %5, vcc\n\t"
+      "v_cmp_ne_u32_sdwa vcc, %4, 0 src0_sel:BYTE_3 src1_sel:DWORD\n\t"
+      "v_cndmask_b32 %3, 0, %5, vcc\n\t"
+      "s_nop 1"
+      : "=&v"(c0), "=&v"(c1), "=&v"(c2), "=&v"(c3)
+      : "v"(mw), "v"(ninf)
+      : "vcc");
+  return (f32x4){c0, c1, c2, c3};
 }
 // maximum / sum over the four lanes (lane >> 4) that share lane & 15
 __device__ __forceinline__ float xa_col_max(float v) {
@@ -105,8 +117,8 @@ __global__ __launch_bounds__(64, 2) void xattn_partial(const XaArgs a) {
   const int j = lane & 15, g = lane >> 4;
   const int seg = blockIdx.x, nh = blockIdx.y, chunk = blockIdx.z;
   const int n = nh / a.H, h = nh - n * a.H;
-  const int l0 = 128 * chunk;                                    // first query of this chunk
-  const int L = min(128, a.L - l0), S = a.S, N = a.N;            // queries of this chunk
+  const int l0 = 16 * NQB * chunk;                               // first query of this chunk
+  const int L = min(16 * NQB, a.L - l0), S = a.S, N = a.N;       // queries of this chunk
   const int E = a.H * HD;
   const long long qrow = (long long)N * a.ldq, krow = (long long)N * a.ldk, vrow = (long long)N * a.ldv;   // floats between sequence positions
   const float* qb_ = a.q + (long long)l0 * qrow + (long long)n * a.ldq + h * HD;
@@ -119,7 +131,7 @@ __global__ __launch_bounds__(64, 2) void xattn_partial(const XaArgs a) {
   const int it0 = (int)((long long)nit * seg / a.nseg), it1 = (int)((long long)nit * (seg + 1) / a.nseg);
 
   // ---- Q fragments: lane's Q[16 qb + j][8 g .. 8 g + 7] * scale * log2e as two fp16 parts -> LDS (B-operand order)
-  float ss = 1.0f, ss_inv = 1.0f;                                // the scores come out of the matrix cores times ss (Q's and K's range scales)
+  float ss_inv = 1.0f;                                           // the scores come out of the matrix cores times Q's and K's range scales
   float sq = 1.0f, sq_inv = 1.0f;
   {
     float qraw[NQB][8];
@@ -152,7 +164,7 @@ __global__ __launch_bounds__(64, 2) void xattn_partial(const XaArgs a) {
 #pragma unroll
     for (int qb = 0; qb < NQB; ++qb) {
       f16x8 h8, m8;
-      xa_split8(qraw[qb], h8, m8);
+      l3_split8(qraw[qb], h8, m8);
       qlds[qb * 64 + lane] = h8;
       qlds[(NQB + qb) * 64 + lane] = m8;
     }
@@ -173,10 +185,21 @@ __global__ __launch_bounds__(64, 2) void xattn_partial(const XaArgs a) {
   // the mask dword of (query 16 qb + j, keys 16 kb + 4 g ..) per query block; loaded one iteration ahead
   float4 kn[2][2], vn[4];
   unsigned mwn[NQB][2];
-  bool mrow[NQB];                                                // my query's mask row counts (see XaArgs.flags)
+  bool mrow[NQB];                                                // my query exists and its mask row counts (see XaArgs.flags)
 #pragma unroll
-  for (int qb = 0; qb < NQB; ++qb)
-    mrow[qb] = a.mask != nullptr && (a.flags == nullptr || a.flags[(long long)n * a.Lfull + min(l0 + 16 * qb + j, a.Lfull - 1)] == a.gen);
+  for (int qb = 0; qb < NQB; ++qb) {
+    const int qi = l0 + 16 * qb + j;
+    mrow[qb] = a.mask != nullptr && qi < a.Lfull && (a.flags == nullptr || a.flags[(long long)n * a.Lfull + qi] == a.gen);
+  }
+  // a lane's four keys are one aligned dword of its query's mask row (rows are padded to a multiple of four bytes when S is not one):
+  // a wave-uniform base per query block (the rows of query l0 + 16 qb) plus one 32-bit lane offset (row j, my keys) for all blocks
+  const int pitch = (S + 3) & ~3;
+  const unsigned char* mask_n = a.mask + ((long long)n * a.Lfull + l0) * pitch;
+  const unsigned joff = (unsigned)j * (unsigned)pitch;
+  // my K row (key s0 + j; the second block's is 16 rows on) and my first V row (key s0 + 16 half + 4 kgl) of the iteration that load_iter
+  // loads next: the iterations of a segment are loaded in order, so the pointers advance by 32 rows instead of being multiplied out per load
+  const float* kp = kb_ + ((long long)(it0 << 5) + j) * krow + 8 * g;
+  const float* vp = vb_ + ((long long)(it0 << 5) + 16 * half + 4 * kgl) * vrow + 4 * hg;
   auto load_iter = [&](int it) __attribute__((always_inline)) {
     const int s0 = it << 5;
 #pragma unroll
@@ -184,7 +207,7 @@ __global__ __launch_bounds__(64, 2) void xattn_partial(const XaArgs a) {
       const int s = s0 + 16 * kb + j;
       kn[kb][0] = kn[kb][1] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (s < S) {
-        const float4* p = reinterpret_cast<const float4*>(kb_ + (long long)s * krow + 8 * g);
+        const float4* p = reinterpret_cast<const float4*>(kp + (long long)(16 * kb) * krow);
         kn[kb][0] = p[0];
         kn[kb][1] = p[1];
       }
@@ -193,26 +216,27 @@ __global__ __launch_bounds__(64, 2) void xattn_partial(const XaArgs a) {
     for (int e = 0; e < 4; ++e) {
       const int s = s0 + 16 * half + 4 * kgl + e;
       vn[e] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (s < S) vn[e] = *reinterpret_cast<const float4*>(vb_ + (long long)s * vrow + 4 * hg);
+      if (s < S) vn[e] = *reinterpret_cast<const float4*>(vp + (long long)e * vrow);
     }
+    kp += 32 * krow;
+    vp += 32 * vrow;
+    const unsigned voff[2] = {joff + (unsigned)min(s0 + 4 * g, pitch - 4), joff + (unsigned)min(s0 + 16 + 4 * g, pitch - 4)};
 #pragma unroll
-    for (int qb = 0; qb < NQB; ++qb)
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb) {
-        mwn[qb][kb] = 0u;
-        if (mrow[qb]) {
-          // a lane's four keys are one aligned dword of its query's mask row (rows are padded to a multiple of four bytes when S is not one)
-          const int qi = min(l0 + 16 * qb + j, a.Lfull - 1);
-          const int pitch = (S + 3) & ~3;
-          const int sbc = min(s0 + 16 * kb + 4 * g, pitch - 4);
-          mwn[qb][kb] = *reinterpret_cast<const unsigned*>(a.mask + ((long long)n * a.Lfull + qi) * pitch + sbc);
-        }
+    for (int qb = 0; qb < NQB; ++qb) {
+      const unsigned char* rows = mask_n + (long long)(16 * qb) * pitch;   // scalar
+      mwn[qb][0] = mwn[qb][1] = 0u;
+      if (mrow[qb]) {
+        mwn[qb][0] = *reinterpret_cast<const unsigned*>(rows + voff[0]);
+        mwn[qb][1] = *reinterpret_cast<const unsigned*>(rows + voff[1]);
       }
+    }
   };
   if (it0 < it1) load_iter(it0);
   __builtin_amdgcn_s_waitcnt(0xc07f);                            // lgkmcnt(0): the Q fragments are in LDS
   __builtin_amdgcn_wave_barrier();
 
+  float ninf = -INFINITY;
+  asm volatile("" : "+v"(ninf));                                 // one register for all the selects of xa_mask_init
 #pragma unroll 1
   for (int it = it0; it < it1; ++it) {
     const int s0 = it << 5;
@@ -234,6 +258,19 @@ __global__ __launch_bounds__(64, 2) void xattn_partial(const XaArgs a) {
       mw[qb][1] = mwn[qb][1];
     }
     if (it + 1 < it1) load_iter(it + 1);                         // scalar
+    // (`; rare`: an assembly comment in every block an ordinary iteration does not enter -- tools/attn_isa_count.py counts the path
+    // without them; being an asm statement it also keeps hipcc from turning the block into selects that every iteration executes)
+    if (s0 + 32 > S) {                                           // scalar: the last iteration of the last segment only -- keys >= S count as masked
+      asm volatile("; rare");
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb) {
+        unsigned beyond = 0u;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) beyond |= (s0 + 16 * kb + 4 * g + r >= S) ? 0xffu << (8 * r) : 0u;
+#pragma unroll
+        for (int qb = 0; qb < NQB; ++qb) mw[qb][kb] |= beyond;
+      }
+    }
 
     // ---- K: two blocks, two fp16 parts
     f16x8 kh[2], km[2];
@@ -245,17 +282,21 @@ __global__ __launch_bounds__(64, 2) void xattn_partial(const XaArgs a) {
 #pragma unroll
         for (int e = 0; e < 8; e += 2) mk = fmaxf(mk, fmaxf(fabsf(kraw[kb][e]), fabsf(kraw[kb][e + 1])));
       if (xa_out_of_range(mk, 0.0625f)) {
+        asm volatile("; rare");
         xa_wave_scale(mk, sk, sk_inv);
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
           for (int e = 0; e < 8; ++e) kraw[kb][e] *= sk;
       }
-      xa_split8(kraw[0], kh[0], km[0]);
-      xa_split8(kraw[1], kh[1], km[1]);
+      l3_split8(kraw[0], kh[0], km[0]);
+      l3_split8(kraw[1], kh[1], km[1]);
     }
-    ss = sq * sk;
     ss_inv = sq_inv * sk_inv;
+    // scalar, and kept a BRANCH below (the empty asm statements): as selects, hipcc multiplied and selected every score and every
+    // accumulator of every query block, 36 vector instructions per block for blocks that are almost never scaled
+    const bool s_scaled = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, sq)) != 0x3f800000 ||
+                          __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, sk)) != 0x3f800000;
 
     // ---- V: 4 keys x 4 channels per lane, transposed into LDS as two fp16 planes
     float sv_inv = 1.0f, sv_fwd = 1.0f;
@@ -267,6 +308,7 @@ __global__ __launch_bounds__(64, 2) void xattn_partial(const XaArgs a) {
       // (an all-zero block -- zero-valued keys -- has nothing to scale: left alone, it no longer multiplies O by 2^54 and back; the
       // scale's exponent is clamped to [-30, 30], so O times the scale stays inside fp32 for any O the earlier blocks left: ADVICE r05)
       if (xa_out_of_range(mv, 0.0625f) && __builtin_amdgcn_ballot_w64(mv > 0.f) != 0) {
+        asm volatile("; rare");
         float sv;
         xa_wave_scale(mv, sv, sv_inv, -16, 44);
         sv_fwd = sv;
@@ -285,11 +327,7 @@ __global__ __launch_bounds__(64, 2) void xattn_partial(const XaArgs a) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) {                              // channel 4 hg + c: four keys
         xa_h4 ch, cm;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          ch[e] = (_Float16)vv[c][e];
-          cm[e] = (_Float16)(vv[c][e] - (float)ch[e]);
-        }
+        l3_split4(vv[c][0], vv[c][1], vv[c][2], vv[c][3], ch, cm);
         *reinterpret_cast<xa_h4*>(dst + c * XA_VS) = ch;
         *reinterpret_cast<xa_h4*>(dst + HD * XA_VS + c * XA_VS) = cm;
       }
@@ -316,20 +354,20 @@ __global__ __launch_bounds__(64, 2) void xattn_partial(const XaArgs a) {
       f32x4 sc[2];
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
-        f32x4 c = {0.f, 0.f, 0.f, 0.f};
+        f32x4 c = xa_mask_init(mw[qb][kb], ninf);                 // -inf for my masked keys (it stays -inf under the finite products), else 0
         c = __builtin_amdgcn_mfma_f32_16x16x32_f16(km[kb], qh, c, 0, 0, 0);   // smallest terms first
         c = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh[kb], qm, c, 0, 0, 0);
         c = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh[kb], qh, c, 0, 0, 0);
-        if (ss != 1.0f) c *= ss_inv;                              // scalar: only blocks that needed a range scale
-        const int sb = s0 + 16 * kb + 4 * g;                     // my four keys
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (((mw[qb][kb] >> (8 * r)) & 0xffu) != 0u || sb + r >= S) c[r] = -INFINITY;
+        if (s_scaled) {                                           // only blocks that needed a range scale
+          asm volatile("; rare");
+          c *= ss_inv;
+        }
         sc[kb] = c;
       }
       float bm = fmaxf(fmaxf(fmaxf(sc[0][0], sc[0][1]), fmaxf(sc[0][2], sc[0][3])), fmaxf(fmaxf(sc[1][0], sc[1][1]), fmaxf(sc[1][2], sc[1][3])));
       bm = xa_col_max(bm);                                       // over the 32 keys, for query j
       if (__builtin_amdgcn_ballot_w64(bm > mref[qb] + 8.0f) != 0) {   // rare after the first blocks: raise reference maxima
+        asm volatile("; rare");
         const float mnew = (bm > mref[qb] + 8.0f) ? bm : mref[qb];
         const float alpha = __builtin_amdgcn_exp2f(mref[qb] - mnew);   // of query j (1 when unchanged; 0 at the very first block)
         mref[qb] = mnew;
@@ -353,7 +391,7 @@ __global__ __launch_bounds__(64, 2) void xattn_partial(const XaArgs a) {
         }
       lsum[qb] += part;
       f16x8 ph, pm;                                              // P[query 16 qb + j][k-slots: block A keys 4 g + e, block B keys 4 g + e]
-      xa_split8(pv, ph, pm);
+      l3_split8<true>(pv, ph, pm);                               // (the values come straight from v_exp_f32)
 #pragma unroll
       for (int hf = 0; hf < 2; ++hf) {
         // A range-scaled V block (wave-uniform): O is taken into the block's units (x scale, a power of two: exact), P V' accumulates
@@ -362,11 +400,17 @@ __global__ __launch_bounds__(64, 2) void xattn_partial(const XaArgs a) {
         // accumulator for the block cost 14 - 30 registers and spilled at seven / eight query blocks (xattn_partial<7>: 49 -> 97 us).
         // (x scale <= 2^54 cannot overflow unless one head holds values 2^70 apart: O <= 2^8 x keys x max |v|.)
         f32x4 o = oacc[qb][hf];
-        if (v_scaled) o *= sv_fwd;
+        if (v_scaled) {
+          asm volatile("; rare");
+          o *= sv_fwd;
+        }
         o = __builtin_amdgcn_mfma_f32_16x16x32_f16(pm, vh[hf], o, 0, 0, 0);
         o = __builtin_amdgcn_mfma_f32_16x16x32_f16(ph, vm[hf], o, 0, 0, 0);
         o = __builtin_amdgcn_mfma_f32_16x16x32_f16(ph, vh[hf], o, 0, 0, 0);
-        if (v_scaled) o *= sv_inv;
+        if (v_scaled) {
+          asm volatile("; rare");
+          o *= sv_inv;
+        }
         oacc[qb][hf] = o;
       }
     }
@@ -401,7 +445,7 @@ __global__ __launch_bounds__(256) void xattn_merge(const float* __restrict__ ws,
   const int q = (int)(t % L);
   const int nh = (int)(t / L);
   const int n = nh / H, h = nh - n * H;
-  const int chunk = q >> 7, ql = q & 127;                        // (one chunk: Lp = 16 * query blocks; several: Lp = 128)
+  const int chunk = q / Lp, ql = q - chunk * Lp;                 // Lp = 16 x (query blocks per wave): the rows of a chunk
   const float* base = ws + ((((long long)chunk * N * H + nh) * nseg) * Lp + ql) * XA_PART;
   const long long pstride = (long long)Lp * XA_PART;
   float M = -INFINITY;
@@ -417,24 +461,54 @@ __global__ __launch_bounds__(256) void xattn_merge(const float* __restrict__ ws,
   out[((long long)q * N + n) * (H * 32) + h * 32 + c] = acc / l;
 }
 
-// segments per (batch entry, head, chunk of 128 queries): one round of the 8 waves per CU the kernel's registers allow, each wave
-// with at least three 32-key iterations (the Q fragments cost about one)
-static int xa_segments(int L, int S, int N, int H) {
-  const int nit = (S + 31) / 32, nchunks = (L + 127) / 128;
-  const int forced = config().xattn_segments;
-  if (forced > 0) return std::min(forced, nit);
-  const long long want = std::max<long long>(1, (8LL * cu_count()) / ((long long)N * H * nchunks));
-  // (short key sequences -- the decoder's self-attention over Q' T = 500 tokens -- are latency-bound: at least 8 segments, 22.8 vs 30.3 us)
-  return (int)std::max<long long>(1, std::min<long long>(want, std::max(nit / 3, std::min(nit, 8))));
+// The launch choice: key segments and query blocks per wave (NQB), measured in profiles/attn_grid_choice_v1.txt (MI355X, the four
+// attention shapes of a 720p clip, every (NQB, segments) pair timed).  What the table shows, and the rule below restates:
+//   * a launch is fastest with about two waves per SIMD in flight, never more -- the waves share the vector issue -- so the segments
+//     fill 2 x SIMDs wave slots, with at least two 32-key iterations per wave;
+//   * a segment count that is a multiple of the 8 XCDs is a local minimum everywhere (workgroups go to the XCDs round-robin: the waves
+//     that read one segment's K / V rows -- the other heads and the other query chunks -- then share an L2);
+//   * among the NQB, a wave's serial length decides: (iterations of its segment) x (K / V preparation + NQB query blocks) + the Q
+//     prologue, where the K / V preparation of one iteration costs 2.2 query blocks (279 against 128 instructions,
+//     profiles/attn_diet_isa_v1.txt) and is repeated per wave; every segment adds a partial per query that the merge reads back
+//     (0.2 us per segment at 40 x 112 rows).  The 1/8 level (460 iterations) keeps seven blocks per wave, the 1/16 level takes four,
+//     the 1/32 level and the self-attention (29 and 16 iterations) one.
+constexpr int XA_MAX_NQB = 7;                                    // (eight blocks do not fit 256 registers: 13 spilled)
+struct XaPlan {
+  int nseg, nqb;
+};
+static XaPlan xa_plan(int L, int S, int N, int H) {
+  const int nit = (S + 31) / 32, blocks = (L + 15) / 16;
+  // UnivsConfig.xattn_segments: the segment count (kernel benchmarks, tests); + 65536 x NQB also fixes the query blocks per wave
+  const int cfg = std::max(0, config().xattn_segments);
+  const int forced = cfg & 0xffff, forced_nqb = std::min((cfg >> 16) & 0xf, XA_MAX_NQB);
+  const double KV = 2.2, PROLOGUE = 0.5, MERGE = 0.2 / 4480.0;
+  const long long simds = 4LL * cu_count();
+  XaPlan best{1, 1};
+  double best_t = 1e300;
+  for (int nqb = 1; nqb <= std::min(blocks, XA_MAX_NQB); ++nqb) {
+    if (forced_nqb > 0 && nqb != std::min(forced_nqb, blocks)) continue;
+    const long long groups = (long long)N * H * ((blocks + nqb - 1) / nqb);
+    int nseg = (int)std::max<long long>(1, std::min<long long>(std::min(nit, nit / 2), 2 * simds / groups));
+    if (nseg >= 8) nseg -= nseg % 8;
+    if (forced > 0) nseg = std::min(forced, nit);
+    const int iters = (nit + nseg - 1) / nseg;
+    const double per_simd = (double)groups * nseg / (double)simds;
+    const double t = (iters * (KV + nqb) + PROLOGUE * nqb) * std::max(1.0, per_simd / 2) + MERGE * nseg * (double)(groups * 16 * nqb);
+    if (t < best_t) {
+      best_t = t;
+      best = XaPlan{nseg, nqb};
+    }
+  }
+  return best;
 }
-int cross_attention_segments(int S, int N, int H) { return xa_segments(1, S, N, H); }
 
 size_t cross_attention_workspace_floats(int L, int S, int N, int H) {
-  const int nqb = (std::min(L, 128) + 15) / 16, nchunks = (L + 127) / 128;
-  return (size_t)nchunks * N * H * xa_segments(L, S, N, H) * (16 * nqb) * XA_PART;
+  const XaPlan p = xa_plan(L, S, N, H);
+  const int nchunks = (L + 16 * p.nqb - 1) / (16 * p.nqb);
+  return (size_t)nchunks * N * H * p.nseg * (16 * p.nqb) * XA_PART;
 }
 
-// returns UNIVS_OK, or UNIVS_ERR_NOT_IMPLEMENTED when the shape is not covered.  Queries beyond 128 are handled in chunks.
+// returns UNIVS_OK, or UNIVS_ERR_NOT_IMPLEMENTED when the shape is not covered.
 int cross_attention_f32(const float* q, const float* k, const float* v, const unsigned char* mask, const unsigned* row_flags,
                         unsigned generation, int L, int S, int N, int H, int hd, int ldq, int ldk, int ldv, float scale, float* ws,
                         float* out, hipStream_t st) {
@@ -443,12 +517,12 @@ int cross_attention_f32(const float* q, const float* k, const float* v, const un
   if (hd != 32 || S < 32 || (mask && ((row_flags && S % 4 != 0) || (reinterpret_cast<uintptr_t>(mask) & 3))) || mis(q) || mis(k) || mis(v) || mis(out) ||
       mis(ws) || (long long)N * H > 65535)
     return UNIVS_ERR_NOT_IMPLEMENTED;
-  const int nseg = xa_segments(L, S, N, H);
+  const XaPlan plan = xa_plan(L, S, N, H);
+  const int nseg = plan.nseg, nqb = plan.nqb;
   const int E = H * 32;
   ldq = ldq > 0 ? ldq : E; ldk = ldk > 0 ? ldk : E; ldv = ldv > 0 ? ldv : E;
   if (ldq < E || ldk < E || ldv < E || ldq % 4 || ldk % 4 || ldv % 4) return UNIVS_ERR_NOT_IMPLEMENTED;
-  const int nchunks = (L + 127) / 128;                           // a workgroup handles up to 128 queries
-  const int nqb = (std::min(L, 128) + 15) / 16;
+  const int nchunks = (L + 16 * nqb - 1) / (16 * nqb);           // a workgroup handles up to 16 nqb queries
   if (nchunks > 65535) return UNIVS_ERR_NOT_IMPLEMENTED;
   XaArgs a{};
   a.q = q; a.k = k; a.v = v;
@@ -468,8 +542,7 @@ int cross_attention_f32(const float* q, const float* k, const float* v, const un
     case 4: hipLaunchKernelGGL(xattn_partial<4>, grid, dim3(64), 0, st, a); break;
     case 5: hipLaunchKernelGGL(xattn_partial<5>, grid, dim3(64), 0, st, a); break;
     case 6: hipLaunchKernelGGL(xattn_partial<6>, grid, dim3(64), 0, st, a); break;
-    case 7: hipLaunchKernelGGL(xattn_partial<7>, grid, dim3(64), 0, st, a); break;
-    default: hipLaunchKernelGGL(xattn_partial<8>, grid, dim3(64), 0, st, a); break;
+    default: hipLaunchKernelGGL(xattn_partial<7>, grid, dim3(64), 0, st, a); break;
   }
   int rc = check_launch("xattn_partial");
   if (rc != UNIVS_OK) return rc;

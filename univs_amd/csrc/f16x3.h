@@ -116,6 +116,89 @@ __device__ __forceinline__ void l3_split8(f32x4 v0, f32x4 v1, float s, f16x8& h,
   m = __builtin_bit_cast(f16x8, mu);
 }
 
+// The same two-instruction split without a scale, for the attention cores (cross_attn.hip, window_attn_f16.hip), whose operands are
+// range-scaled beforehand where they need it: two values -> one packed pair of first parts h = fp16(x) and one of second parts
+// m = fp16(x - h).  The same bits as `h = (_Float16)x; m = (_Float16)(x - (float)h)`: fp16(x 1 + 0) is the one rounding of the
+// conversion, and x - h is exact in fp32 (h holds x's leading 11 bits), so fp16(fma(x, 1, -h)) rounds the same number once.
+__device__ __forceinline__ void l3_split2(float x0, float x1, unsigned& hp, unsigned& mp) {
+  asm("v_fma_mixlo_f16 %0, %2, 1.0, 0 op_sel_hi:[0,0,0]\n\t"
+      "v_fma_mixhi_f16 %0, %3, 1.0, 0 op_sel_hi:[0,0,0]\n\t"
+      "v_fma_mixlo_f16 %1, %2, 1.0, -%0 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
+      "v_fma_mixhi_f16 %1, %3, 1.0, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
+      : "=&v"(hp), "=&v"(mp)
+      : "v"(x0), "v"(x1));
+}
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+// PADDED: for values that come straight from a transcendental instruction (v_exp_f32: no vector instruction may read its result in
+// the very next slot) and parts that go straight into a matrix instruction (two wait states after the vector write).  hipcc keeps such
+// distances between its own instructions only, not around an asm statement, so the split is ONE statement that opens and closes with them.
+template <bool PADDED = false>
+__device__ __forceinline__ void l3_split8(const float (&x)[8], f16x8& h, f16x8& m) {
+  u32x4 hu, mu;
+  if constexpr (PADDED) {
+    unsigned h0, h1, h2, h3, m0, m1, m2, m3;
+    asm("s_nop 0\n\t"
+        "v_fma_mixlo_f16 %0, %8, 1.0, 0 op_sel_hi:[0,0,0]\n\t"
+        "v_fma_mixhi_f16 %0, %9, 1.0, 0 op_sel_hi:[0,0,0]\n\t"
+        "v_fma_mixlo_f16 %4, %8, 1.0, -%0 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
+        "v_fma_mixhi_f16 %4, %9, 1.0, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
+        "v_fma_mixlo_f16 %1, %10, 1.0, 0 op_sel_hi:[0,0,0]\n\t"
+        "v_fma_mixhi_f16 %1, %11, 1.0, 0 op_sel_hi:[0,0,0]\n\t"
+        "v_fma_mixlo_f16 %5, %10, 1.0, -%1 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
+        "v_fma_mixhi_f16 %5, %11, 1.0, -%1 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
+        "v_fma_mixlo_f16 %2, %12, 1.0, 0 op_sel_hi:[0,0,0]\n\t"
+        "v_fma_mixhi_f16 %2, %13, 1.0, 0 op_sel_hi:[0,0,0]\n\t"
+        "v_fma_mixlo_f16 %6, %12, 1.0, -%2 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
+        "v_fma_mixhi_f16 %6, %13, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
+        "v_fma_mixlo_f16 %3, %14, 1.0, 0 op_sel_hi:[0,0,0]\n\t"
+        "v_fma_mixhi_f16 %3, %15, 1.0, 0 op_sel_hi:[0,0,0]\n\t"
+        "v_fma_mixlo_f16 %7, %14, 1.0, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
+        "v_fma_mixhi_f16 %7, %15, 1.0, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
+        "s_nop 1"
+        : "=&v"(h0), "=&v"(h1), "=&v"(h2), "=&v"(h3), "=&v"(m0), "=&v"(m1), "=&v"(m2), "=&v"(m3)
+        : "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]), "v"(x[4]), "v"(x[5]), "v"(x[6]), "v"(x[7]));
+    hu = (u32x4){h0, h1, h2, h3};
+    mu = (u32x4){m0, m1, m2, m3};
+  } else {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      unsigned hp, mp;
+      l3_split2(x[2 * p], x[2 * p + 1], hp, mp);
+      hu[p] = hp;
+      mu[p] = mp;
+    }
+  }
+  h = __builtin_bit_cast(f16x8, hu);
+  m = __builtin_bit_cast(f16x8, mu);
+}
+template <bool PADDED = false>
+__device__ __forceinline__ void l3_split4(float x0, float x1, float x2, float x3, f16x4& h, f16x4& m) {
+  u32x2 hu, mu;
+  unsigned h0, h1, m0, m1;
+  if constexpr (PADDED) {
+    asm("s_nop 0\n\t"
+        "v_fma_mixlo_f16 %0, %4, 1.0, 0 op_sel_hi:[0,0,0]\n\t"
+        "v_fma_mixhi_f16 %0, %5, 1.0, 0 op_sel_hi:[0,0,0]\n\t"
+        "v_fma_mixlo_f16 %2, %4, 1.0, -%0 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
+        "v_fma_mixhi_f16 %2, %5, 1.0, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
+        "v_fma_mixlo_f16 %1, %6, 1.0, 0 op_sel_hi:[0,0,0]\n\t"
+        "v_fma_mixhi_f16 %1, %7, 1.0, 0 op_sel_hi:[0,0,0]\n\t"
+        "v_fma_mixlo_f16 %3, %6, 1.0, -%1 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
+        "v_fma_mixhi_f16 %3, %7, 1.0, -%1 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
+        "s_nop 1"
+        : "=&v"(h0), "=&v"(h1), "=&v"(m0), "=&v"(m1)
+        : "v"(x0), "v"(x1), "v"(x2), "v"(x3));
+  } else {
+    l3_split2(x0, x1, h0, m0);
+    l3_split2(x2, x3, h1, m1);
+  }
+  hu = (u32x2){h0, h1};
+  mu = (u32x2){m0, m1};
+  h = __builtin_bit_cast(f16x4, hu);
+  m = __builtin_bit_cast(f16x4, mu);
+}
+
 __device__ __forceinline__ unsigned l3_absmax8(f32x4 v0, f32x4 v1) {
 #ifdef UNIVS_ABLATE_NOSPLIT
   return 0x3f800000u;

@@ -133,7 +133,11 @@ __global__ __launch_bounds__(64 * NWV) void window_attn_img_f16(const float* __r
 #pragma unroll
     for (int r = 0; r < VR; ++r) {
       const bool hi_ok = r + VR < NB;                          // compile time
-      const int src = hi_ok ? (half ? tok[hi_ok ? r + VR : r] : tok[r]) : tok[r];
+      // (the two candidates are made opaque first: hipcc turned the select between two elements of tok[] into a load from a copy
+      // of the array in scratch, indexed by `half`)
+      int t_lo = tok[r], t_hi = tok[hi_ok ? r + VR : r];
+      asm volatile("" : "+v"(t_lo), "+v"(t_hi));
+      const int src = (hi_ok && half) ? t_hi : t_lo;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int t = __shfl(src, half * 32 + kgl * 4 + e, 64);
@@ -176,10 +180,11 @@ __global__ __launch_bounds__(64 * NWV) void window_attn_img_f16(const float* __r
 #pragma unroll
         for (int c = 0; c < 4; ++c) {                          // channel 4 hg + c: four keys
           f16x4 ch, cm;
+          if constexpr (TERMS == 3) {                          // both parts in two instructions per value (f16x3.h)
+            l3_split4(vv[c][0], vv[c][1], vv[c][2], vv[c][3], ch, cm);
+          } else {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            ch[e] = (_Float16)vv[c][e];
-            cm[e] = (_Float16)(vv[c][e] - (float)ch[e]);
+            for (int e = 0; e < 4; ++e) ch[e] = (_Float16)vv[c][e];
           }
           *reinterpret_cast<f16x4*>(dst + c * VS) = ch;
           if (TERMS == 3) *reinterpret_cast<f16x4*>(dst + HD * VS + c * VS) = cm;
@@ -220,12 +225,14 @@ __global__ __launch_bounds__(64 * NWV) void window_attn_img_f16(const float* __r
         }
       }
 #pragma unroll
-      for (int jb = 0; jb < NB; ++jb)
+      for (int jb = 0; jb < NB; ++jb) {
+        if constexpr (TERMS == 3) {
+          l3_split8(kraw[jb], kf[jb], kfm[jb]);
+        } else {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          kf[jb][e] = (_Float16)kraw[jb][e];
-          if (TERMS == 3) kfm[jb][e] = (_Float16)(kraw[jb][e] - (float)kf[jb][e]);
+          for (int e = 0; e < 8; ++e) kf[jb][e] = (_Float16)kraw[jb][e];
         }
+      }
     }
     // Q of the first query block (the loop below requests block ib + 1 while it computes block ib)
     float4 qa = make_float4(0.f, 0.f, 0.f, 0.f), qc = qa;
@@ -272,10 +279,11 @@ __global__ __launch_bounds__(64 * NWV) void window_attn_img_f16(const float* __r
           ss = sk * sq;                                         // the scores come out of the matrix cores times ss
           ss_inv = sk_inv * sq_inv;
         }
+        if constexpr (TERMS == 3) {
+          l3_split8<true>(qq, qf, qfm);                          // (the parts go straight into the matrix instructions)
+        } else {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          qf[e] = (_Float16)qq[e];
-          qfm[e] = (_Float16)(qq[e] - (float)qf[e]);
+          for (int e = 0; e < 8; ++e) qf[e] = (_Float16)qq[e];
         }
       }
       if (ib + 1 < NB) {                // scalar
@@ -340,12 +348,17 @@ __global__ __launch_bounds__(64 * NWV) void window_attn_img_f16(const float* __r
       f16x4 p[NB], pm[TERMS == 3 ? NB : 1];
 #pragma unroll
       for (int jb = 0; jb < NB; ++jb) {
+        float e[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float e = __builtin_amdgcn_exp2f(s[jb][r] - mx);   // exp2(-inf) = 0 for padded keys
-          sum += e;
-          p[jb][r] = (_Float16)e;
-          if (TERMS == 3) pm[jb][r] = (_Float16)(e - (float)p[jb][r]);
+          e[r] = __builtin_amdgcn_exp2f(s[jb][r] - mx);          // exp2(-inf) = 0 for padded keys
+          sum += e[r];
+        }
+        if constexpr (TERMS == 3) {
+          l3_split4<true>(e[0], e[1], e[2], e[3], p[jb], pm[jb]);   // (from v_exp_f32 into the matrix instructions)
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) p[jb][r] = (_Float16)e[r];
         }
       }
       sum += __shfl_xor(sum, 16);
