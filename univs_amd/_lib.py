@@ -1,4 +1,5 @@
-"""ctypes binding of libunivs_hip.so (the C ABI declared in include/univs_hip.h and include/univs_eval_hip.h).
+"""ctypes binding of libunivs_hip.so (the C ABI declared in include/univs_hip.h, include/univs_eval_hip.h and
+include/univs_fused_hip.h).
 
 The header is the one statement of the ABI: `SIGNATURES` (restype / argtypes of every `univs_*` symbol) and `CONFIG_FIELDS` (the
 members of `struct UnivsConfig`) are read from its text when this module loads -- no table is kept by hand.
@@ -77,6 +78,10 @@ CONFIG_FIELDS = parse_config_fields(_HEADER)
 EVAL_HEADER_PATH = os.path.join(_HERE, "..", "include", "univs_eval_hip.h")
 with open(EVAL_HEADER_PATH) as _f:
     EVAL_SIGNATURES = parse_signatures(_f.read())
+# The third header (include/univs_fused_hip.h: consumers that fold a producer's transform into their operand load), likewise.
+FUSED_HEADER_PATH = os.path.join(_HERE, "..", "include", "univs_fused_hip.h")
+with open(FUSED_HEADER_PATH) as _f:
+    FUSED_SIGNATURES = parse_signatures(_f.read())
 
 _lib = None
 
@@ -96,7 +101,7 @@ def load():
             f"{LIB_PATH} not found: the HIP extension is mandatory (no CPU fallback). "
             "Build it with `python -m univs_amd.build`.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in (*SIGNATURES.items(), *EVAL_SIGNATURES.items()):
+    for name, (res, args) in (*SIGNATURES.items(), *EVAL_SIGNATURES.items(), *FUSED_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing -> loud
         fn.restype = res
         fn.argtypes = args

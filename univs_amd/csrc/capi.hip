@@ -6,6 +6,7 @@
 #include <mutex>
 
 #include "../../include/univs_eval_hip.h"
+#include "../../include/univs_fused_hip.h"
 #include "common.h"
 #include "config.h"
 #include "launchers.h"
@@ -320,6 +321,49 @@ int univs_conv3x3_nhwc_presplit_f32(const float* x, const void* wp, const float*
   const Entry e("univs_conv3x3_nhwc_presplit_f32", stream);
   return conv_entry(e, "Cin % 128, Cout % 16, >= 4096 pixels", T, Cin, Cout, H, W, x && wp && winv && y,
                     [&] { return conv3x3_nhwc_f16x3_f32(x, wp, winv, y, T, Cin, Cout, H, W, e.st); });
+}
+
+int univs_conv1x1_fused_presplit_f32(const float* x, int channels_last, const float* affine, const void* wp, const float* winv,
+                                     const float* bias, int T, int Cin, int Cout, int H, int W, float* y, void* stream) {
+  const Entry e("univs_conv1x1_fused_presplit_f32", stream);
+  return conv_entry(e, "Cin % 96 or % 128, Cout % 16, >= 4096 pixels; with an affine H W >= 256 and Cin <= 1024", T, Cin, Cout, H, W,
+                    x && wp && winv && y,
+                    [&] { return conv1x1_fused_f16x3_f32(x, channels_last, affine, wp, winv, bias, y, T, Cin, Cout, H, W, e.st); });
+}
+
+int univs_cross_attention_partials_f32(const float* q, const float* k, const float* v, const uint8_t* mask, const uint32_t* mask_row_flags,
+                                       uint32_t mask_generation, int L, int S, int N, int H, int head_dim, int ldq, int ldk, int ldv,
+                                       float scale, float* workspace, int* plan, void* stream) {
+  const Entry e("univs_cross_attention_partials_f32", stream);
+  if (!plan) return e.invalid("NULL plan (a host int)");
+  *plan = 0;
+  if (L < 0 || S < 1 || N < 0 || H < 1 || head_dim < 1) return e.invalid("bad dimensions L=%d S=%d N=%d H=%d head_dim=%d", L, S, N, H, head_dim);
+  if (L == 0 || N == 0) return UNIVS_OK;
+  if (!q || !k || !v || !workspace || (mask_row_flags && !mask)) return e.invalid("NULL data pointer (row flags come with a mask)");
+  return e.covered(cross_attention_partials_f32(q, k, v, mask, mask_row_flags, mask_generation, L, S, N, H, head_dim, ldq, ldk, ldv, scale,
+                                                workspace, plan, e.st),
+                   "L=%d S=%d N=%d H=%d head_dim=%d not covered (head_dim == 32, S >= 32, with a mask S %% 4 == 0, "
+                   "N * H <= 65535, 16-byte aligned pointers)", L, S, N, H, head_dim);
+}
+
+int univs_small_linear_merged_presplit_f32(const float* workspace, long long workspace_floats, int plan, int L, int N, int H, const void* wp,
+                                           const float* winv, const float* bias, int n_w, int f_off, const float* residual,
+                                           const float* ln_weight, const float* ln_bias, float ln_eps, int n_out, float* y, void* stream) {
+  const Entry e("univs_small_linear_merged_presplit_f32", stream);
+  const int nseg = plan & 0xffff, nqb = plan >> 16;
+  if (L < 0 || N < 0 || H < 1 || n_out < 0 || n_w < 1 || f_off < 0 || f_off + n_out > n_w)
+    return e.invalid("bad arguments L=%d N=%d H=%d n_out=%d n_w=%d f_off=%d", L, N, H, n_out, n_w, f_off);
+  if (L == 0 || N == 0 || n_out == 0) return UNIVS_OK;
+  if (plan <= 0 || nseg < 1 || nqb < 1 || nqb > 7) return e.invalid("plan=%d is not segments + 65536 * query blocks per wave (1 .. 7)", plan);
+  const long long chunks = ((long long)L + 16 * nqb - 1) / (16 * nqb);
+  const long long need = chunks * N * H * nseg * (16 * nqb) * 34;
+  if (workspace_floats < need)
+    return e.invalid("workspace of %lld floats, the plan %d of L=%d N=%d H=%d takes %lld", workspace_floats, plan, L, N, H, need);
+  if (!workspace || !wp || !winv || !y || (ln_bias && !ln_weight)) return e.null_pointer();
+  return e.covered(small_linear_merged_f32(workspace, plan, L, N, H, wp, winv, bias, n_w, f_off, residual, ln_weight, ln_bias, ln_eps, y,
+                                           n_out, e.st),
+                   "L=%d N=%d H=%d n_out=%d not covered (H <= 8, n_out %% 16 == 0, f_off %% 4 == 0, with a LayerNorm n_out == 256, "
+                   "L N <= 1 048 560, 16-byte aligned pointers)", L, N, H, n_out);
 }
 
 int univs_patch_embed4_f32(const float* x, const float* weight, const float* bias, const float* ln_weight, const float* ln_bias, float ln_eps,

@@ -30,6 +30,7 @@
 //     (out = sum_p O_p 2^(m_p - M) / sum_p l_p 2^(m_p - M)) and stores [L, N, h d].
 #include "common.h"
 #include "launchers.h"
+#include "xattn_merge.h"
 #include "config.h"
 #include "f16x3.h"
 
@@ -55,7 +56,6 @@ struct XaArgs {
   float qscale;              // scale * log2(e)
 };
 
-constexpr int XA_PART = 34;
 #ifndef UNIVS_XA_VS
 #define UNIVS_XA_VS 36
 #endif
@@ -448,17 +448,9 @@ __global__ __launch_bounds__(256) void xattn_merge(const float* __restrict__ ws,
   const int chunk = q / Lp, ql = q - chunk * Lp;                 // Lp = 16 x (query blocks per wave): the rows of a chunk
   const float* base = ws + ((((long long)chunk * N * H + nh) * nseg) * Lp + ql) * XA_PART;
   const long long pstride = (long long)Lp * XA_PART;
-  float M = -INFINITY;
-#pragma unroll 8                                                 // (independent loads in flight: the kernel is pure latency)
-  for (int p = 0; p < nseg; ++p) M = fmaxf(M, base[p * pstride + 32]);
-  float acc = 0.f, l = 0.f;
-#pragma unroll 8
-  for (int p = 0; p < nseg; ++p) {
-    const float f = __builtin_amdgcn_exp2f(base[p * pstride + 32] - M);
-    acc = fmaf(base[p * pstride + c], f, acc);
-    l = fmaf(base[p * pstride + 33], f, l);
-  }
-  out[((long long)q * N + n) * (H * 32) + h * 32 + c] = acc / l;
+  float r[1];
+  xa_merge_partials<1>(base, pstride, nseg, c, r);               // (xattn_merge.h)
+  out[((long long)q * N + n) * (H * 32) + h * 32 + c] = r[0];
 }
 
 // The launch choice: key segments and query blocks per wave (NQB), measured in profiles/attn_grid_choice_v1.txt (MI355X, the four
@@ -508,13 +500,16 @@ size_t cross_attention_workspace_floats(int L, int S, int N, int H) {
   return (size_t)nchunks * N * H * p.nseg * (16 * p.nqb) * XA_PART;
 }
 
-// returns UNIVS_OK, or UNIVS_ERR_NOT_IMPLEMENTED when the shape is not covered.
-int cross_attention_f32(const float* q, const float* k, const float* v, const unsigned char* mask, const unsigned* row_flags,
-                        unsigned generation, int L, int S, int N, int H, int hd, int ldq, int ldk, int ldv, float scale, float* ws,
-                        float* out, hipStream_t st) {
+// The partials alone: the segments' records in `ws`, merged by the caller's next launch (xattn_merge, or the out-projection that merges
+// while it stages its operand: small_linear.hip).  *plan = segments + 65536 x query blocks per wave, the packing of
+// UnivsConfig.xattn_segments.  Returns UNIVS_OK, or UNIVS_ERR_NOT_IMPLEMENTED when the shape is not covered.
+int cross_attention_partials_f32(const float* q, const float* k, const float* v, const unsigned char* mask, const unsigned* row_flags,
+                                 unsigned generation, int L, int S, int N, int H, int hd, int ldq, int ldk, int ldv, float scale, float* ws,
+                                 int* plan_out, hipStream_t st) {
+  if (plan_out) *plan_out = 0;
   if (L <= 0 || N <= 0 || H <= 0) return UNIVS_OK;
   auto mis = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
-  if (hd != 32 || S < 32 || (mask && ((row_flags && S % 4 != 0) || (reinterpret_cast<uintptr_t>(mask) & 3))) || mis(q) || mis(k) || mis(v) || mis(out) ||
+  if (hd != 32 || S < 32 || (mask && ((row_flags && S % 4 != 0) || (reinterpret_cast<uintptr_t>(mask) & 3))) || mis(q) || mis(k) || mis(v) ||
       mis(ws) || (long long)N * H > 65535)
     return UNIVS_ERR_NOT_IMPLEMENTED;
   const XaPlan plan = xa_plan(L, S, N, H);
@@ -529,7 +524,7 @@ int cross_attention_f32(const float* q, const float* k, const float* v, const un
   a.mask = mask;
   a.flags = mask ? row_flags : nullptr;
   a.gen = generation;
-  a.ws = ws; a.out = out;
+  a.ws = ws; a.out = nullptr;                                    // (the partial kernels write ws alone)
   a.L = L; a.S = S; a.N = N; a.H = H; a.nseg = nseg;
   a.Lfull = L; a.l0 = 0;
   a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
@@ -544,8 +539,20 @@ int cross_attention_f32(const float* q, const float* k, const float* v, const un
     case 6: hipLaunchKernelGGL(xattn_partial<6>, grid, dim3(64), 0, st, a); break;
     default: hipLaunchKernelGGL(xattn_partial<7>, grid, dim3(64), 0, st, a); break;
   }
-  int rc = check_launch("xattn_partial");
+  if (plan_out) *plan_out = nseg + 65536 * nqb;
+  return check_launch("xattn_partial");
+}
+
+// returns UNIVS_OK, or UNIVS_ERR_NOT_IMPLEMENTED when the shape is not covered.
+int cross_attention_f32(const float* q, const float* k, const float* v, const unsigned char* mask, const unsigned* row_flags,
+                        unsigned generation, int L, int S, int N, int H, int hd, int ldq, int ldk, int ldv, float scale, float* ws,
+                        float* out, hipStream_t st) {
+  if (L <= 0 || N <= 0 || H <= 0) return UNIVS_OK;
+  if (reinterpret_cast<uintptr_t>(out) & 15) return UNIVS_ERR_NOT_IMPLEMENTED;
+  int plan = 0;
+  const int rc = cross_attention_partials_f32(q, k, v, mask, row_flags, generation, L, S, N, H, hd, ldq, ldk, ldv, scale, ws, &plan, st);
   if (rc != UNIVS_OK) return rc;
+  const int nseg = plan & 0xffff, nqb = plan >> 16;
   const long long total = (long long)N * H * L * 32;
   hipLaunchKernelGGL(xattn_merge, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ws, out, L, 16 * nqb, N, H, nseg);
   return check_launch("xattn_merge");

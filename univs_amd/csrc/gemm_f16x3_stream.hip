@@ -81,10 +81,14 @@ struct GsArgs {
   int Cin, Cout, H, Wd, HW;      // conv (XMODE 1): X [T, Cin, H, W], Y [T, Cout, H, W]; XMODE 2: X [T, H, W, Cin] (channels last), Y as XMODE 1
   int tap0;                      // conv: first tap of the kernel (0: all nine taps of a 3 x 3; 4: the centre alone = a 1 x 1)
   int remap;                     // XCD-aware (row range, pass) order (UnivsConfig.linear_ablate == 5 switches it off: A/B)
+  const float* affine;           // AFF (a 1 x 1 on XMODE 1 / 2): (scale, bias) of every (frame, input channel) plane, [T * Cin][2]
 };
 
-// LDS: 2 x [RING][4 k-groups][2 parts][16 RB] 16 B | bias[Rp] | winv[Rp]
-template <int RB, int RING, int XMODE>
+// LDS: 2 x [RING][4 k-groups][2 parts][16 RB] 16 B | bias[Rp] | winv[Rp] | AFF: (scale, bias)[2 frames][Cin]
+// AFF: x is the RAW output of a convolution and the operand is relu(GroupNorm(x)) = fmaxf(fmaf(x, scale, bias), 0) with the pairs of
+// group_norm_affine_f32 -- the expression of gn_apply_kernel (group_norm.hip), so the product is that of the materialised tensor bit
+// for bit.  The pairs of the (at most two) frames the workgroup's 256 rows of a round lie in are staged in LDS, frame f in slot f & 1.
+template <int RB, int RING, int XMODE, bool AFF = false>
 __global__ __launch_bounds__(GS_THREADS, 512 / GS_THREADS) void gemm_f16x3_stream(const GsArgs a) {
   extern __shared__ __attribute__((aligned(16))) u32x4 Wst[];
   [[maybe_unused]] const int gts = UNIVS_GT_SLOT();
@@ -108,6 +112,7 @@ __global__ __launch_bounds__(GS_THREADS, 512 / GS_THREADS) void gemm_f16x3_strea
   const int j = lane & 15, g = lane >> 4;
   float* bias_lds = reinterpret_cast<float*>(Wst + 2 * SLAB);
   float* winv_lds = bias_lds + Rp;
+  [[maybe_unused]] float* aff_lds = winv_lds + Rp;
   constexpr int NWV = GS_THREADS / 64;
 
   const int WT = (M + GS_TILE_M - 1) / GS_TILE_M;
@@ -165,6 +170,7 @@ __global__ __launch_bounds__(GS_THREADS, 512 / GS_THREADS) void gemm_f16x3_strea
   struct TileRows {
     unsigned vo[2];
     int py[2], px[2];
+    unsigned ao[2];                                              // AFF: byte offset of the pair of (frame slot, channel 8 g) in aff_lds
   };
   auto tile_rows = [&](int tt, TileRows& t) __attribute__((always_inline)) {
 #pragma unroll
@@ -173,16 +179,19 @@ __global__ __launch_bounds__(GS_THREADS, 512 / GS_THREADS) void gemm_f16x3_strea
       if (XMODE == 0) {
         t.vo[c] = ((unsigned)m * (unsigned)K + (unsigned)(8 * g)) * 4u;
         t.py[c] = t.px[c] = 0;
+        t.ao[c] = 0u;
       } else if (XMODE == 2) {
         const int f = m / a.HW, rem = m - f * a.HW;
-        t.py[c] = rem / a.Wd;
-        t.px[c] = rem - t.py[c] * a.Wd;
+        t.py[c] = AFF ? 0 : rem / a.Wd;                          // (AFF is a 1 x 1: the only tap is the pixel itself)
+        t.px[c] = AFF ? 0 : rem - t.py[c] * a.Wd;
         t.vo[c] = ((unsigned)m * (unsigned)a.Cin + (unsigned)(8 * g)) * 4u;   // pixel m, channels 8 g ..: 32 contiguous bytes
+        t.ao[c] = (unsigned)(((f & 1) * a.Cin + 8 * g) * 8);
       } else {
         const int f = m / a.HW, rem = m - f * a.HW;
-        t.py[c] = rem / a.Wd;
-        t.px[c] = rem - t.py[c] * a.Wd;
+        t.py[c] = AFF ? 0 : rem / a.Wd;
+        t.px[c] = AFF ? 0 : rem - t.py[c] * a.Wd;
         t.vo[c] = (unsigned)((f * a.Cin + 8 * g) * a.HW + rem) * 4u;
+        t.ao[c] = (unsigned)(((f & 1) * a.Cin + 8 * g) * 8);
       }
     }
   };
@@ -203,7 +212,7 @@ __global__ __launch_bounds__(GS_THREADS, 512 / GS_THREADS) void gemm_f16x3_strea
       const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
-        const bool inb = (unsigned)(t.py[c] + dy) < (unsigned)a.H && (unsigned)(t.px[c] + dx) < (unsigned)a.Wd;
+        const bool inb = AFF || ((unsigned)(t.py[c] + dy) < (unsigned)a.H && (unsigned)(t.px[c] + dx) < (unsigned)a.Wd);
         const unsigned vo = inb ? t.vo[c] + (unsigned)((dy * a.Wd + dx) * a.Cin * 4) : 0xFFFFFFE0u;
         buf[c][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, vo, cb * 4, 0));
         buf[c][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, vo + 16u, cb * 4, 0));
@@ -215,7 +224,7 @@ __global__ __launch_bounds__(GS_THREADS, 512 / GS_THREADS) void gemm_f16x3_strea
       const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
-        const bool inb = (unsigned)(t.py[c] + dy) < (unsigned)a.H && (unsigned)(t.px[c] + dx) < (unsigned)a.Wd;
+        const bool inb = AFF || ((unsigned)(t.py[c] + dy) < (unsigned)a.H && (unsigned)(t.px[c] + dx) < (unsigned)a.Wd);
         const unsigned vo = inb ? t.vo[c] + (unsigned)((dy * a.Wd + dx) * 4) : 0xFFFFFFF0u;
 #pragma unroll
         for (int e = 0; e < 8; ++e)
@@ -267,10 +276,28 @@ __global__ __launch_bounds__(GS_THREADS, 512 / GS_THREADS) void gemm_f16x3_strea
   UNIVS_GT(g_gs_trace, gts, 2);
   UNIVS_GT_VAL(g_gs_trace, gts, 63, rounds);
   int gq = 0;                                                    // k-groups done: slab gq is in buffer gq & 1
+  [[maybe_unused]] int aff_f0 = -1, aff_f1 = -1;                 // AFF: the frames whose pairs are staged
 #pragma unroll 1
   for (int rd = 0; rd < rounds; ++rd) {
     const int tt = wg0 + rd * NWV + wave;
     const bool tile_ok = tt < wg1;
+    if constexpr (AFF) {
+      // the frames of this round's rows (idle tiles and rows past the end included: they repeat row M - 1); HW >= NWV * GS_TILE_M,
+      // so at most two.  Re-staged only where the range moves on: behind a barrier (the round before has read its pairs), and the
+      // first barrier of the k-group loop below publishes the new ones
+      const int r0 = min((wg0 + rd * NWV) * GS_TILE_M, M - 1), r1 = min(r0 + NWV * GS_TILE_M - 1, M - 1);
+      const int f0 = r0 / a.HW, f1 = r1 / a.HW;
+      if (f0 != aff_f0 || f1 != aff_f1) {
+        __syncthreads();
+        const int n = (f1 - f0 + 1) * a.Cin;
+        for (int i = tid; i < n; i += GS_THREADS) {
+          const int f = i < a.Cin ? f0 : f1, ch = i < a.Cin ? i : i - a.Cin;
+          *reinterpret_cast<float2*>(aff_lds + ((f & 1) * a.Cin + ch) * 2) = *reinterpret_cast<const float2*>(a.affine + ((size_t)f * a.Cin + ch) * 2);
+        }
+        aff_f0 = f0;
+        aff_f1 = f1;
+      }
+    }
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) acc[rb][0] = acc[rb][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
     eset[0] = eset[1] = -1000;
@@ -285,6 +312,23 @@ __global__ __launch_bounds__(GS_THREADS, 512 / GS_THREADS) void gemm_f16x3_strea
 #pragma unroll
       for (int u = 0; u < RING; ++u) {
         if (u > 0) w_commit(bufc ^ 1, u - 1);
+        if constexpr (AFF) {
+          // k-step q * RING + u = input channels 32 (q * RING + u) ..: my eight pairs are 64 contiguous bytes of my frame's slot
+          const unsigned kb = (unsigned)((q * RING + u) * 32 * 8);
+#pragma unroll
+          for (int c = 0; c < 2; ++c) {
+            const f32x4* ap = reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(aff_lds) + t_cur.ao[c] + kb);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+              const f32x4 p0 = ap[2 * h], p1 = ap[2 * h + 1];
+              raw[u][c][h][0] = fmaxf(fma_single(raw[u][c][h][0], p0[0], p0[1]), 0.f);
+              raw[u][c][h][1] = fmaxf(fma_single(raw[u][c][h][1], p0[2], p0[3]), 0.f);
+              raw[u][c][h][2] = fmaxf(fma_single(raw[u][c][h][2], p1[0], p1[1]), 0.f);
+              raw[u][c][h][3] = fmaxf(fma_single(raw[u][c][h][3], p1[2], p1[3]), 0.f);
+            }
+            __builtin_amdgcn_sched_barrier(0);                   // one column tile's pairs at a time: registers
+          }
+        }
         // ---- the running row scale (linear_f16x3.hip)
         bool need = false;
         int enew[2];
@@ -407,20 +451,23 @@ __global__ __launch_bounds__(GS_THREADS, 512 / GS_THREADS) void gemm_f16x3_strea
   UNIVS_GT_REAL(g_gs_trace, gts, 61);
 }
 
-template <int XMODE>
+template <int XMODE, bool AFF = false>
 static int gs_launch(const GsArgs& a0, hipStream_t st) {
   GsArgs a = a0;
   const StreamPlan p = plan_stream(XMODE, a.M, a.N, a.K, cu_count(), config());
   a.rows_per_pass = p.rows_per_pass;
   a.remap = p.remap;
   const int RB = p.RB, ring = p.ring;
-  const size_t lds = p.lds;
+  const size_t lds = p.lds + (AFF ? gs_affine_lds(a.Cin) : 0);
+  if (AFF && !stream_affine_plan_covered(RB, ring)) return UNIVS_ERR_NOT_IMPLEMENTED;
   dim3 grid(p.gx, p.passes), block(GS_THREADS);
 #define UNIVS_GS(rb, rg)                                                                                          \
   do {                                                                                                            \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16x3_stream<rb, rg, XMODE>),                   \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                              \
-    hipLaunchKernelGGL((gemm_f16x3_stream<rb, rg, XMODE>), grid, block, lds, st, a);                              \
+    if constexpr (!AFF || stream_affine_plan_covered(rb, rg)) {                                                   \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16x3_stream<rb, rg, XMODE, AFF>),            \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                            \
+      hipLaunchKernelGGL((gemm_f16x3_stream<rb, rg, XMODE, AFF>), grid, block, lds, st, a);                       \
+    }                                                                                                             \
   } while (0)
 #define UNIVS_GS_RB(rb)                    \
   case rb:                                 \
@@ -457,18 +504,22 @@ int linear_f16x3_stream_f32(const float* x, const void* wp, const float* winv, c
 
 // The convolutions: the same GEMM with tap addressing of x [T, Cin, H, W] (XMODE 1) or [T, H, W, Cin] (XMODE 2), y [T, Cout, H, W];
 // `taps` = 9: a 3 x 3 (stride 1, padding 1); 1: the centre tap alone = a 1 x 1 (K = Cin; w pre-split as a Linear's [Cout, Cin])
+// `affine` (a 1 x 1 only): the operand is fmaxf(fmaf(x, scale, bias), 0) with the (scale, bias) of x's (frame, channel) plane
 template <int XMODE>
 static int gs_conv(const float* x, const void* wp, const float* winv, const float* bias, float* y, int T, int Cin, int Cout, int H, int W,
-                   int taps, hipStream_t st) {
+                   int taps, hipStream_t st, const float* affine = nullptr) {
   if (T <= 0 || Cout <= 0 || H <= 0 || W <= 0) return UNIVS_OK;
   const long long M = (long long)T * H * W;
   if (!stream_conv_covered(M, Cin, Cout, taps) || !aligned16(x, wp, y, winv, bias)) return UNIVS_ERR_NOT_IMPLEMENTED;
+  if (affine && (taps != 1 || !stream_affine_covered((long long)H * W, Cin) || (reinterpret_cast<uintptr_t>(affine) & 7)))
+    return UNIVS_ERR_NOT_IMPLEMENTED;
   GsArgs a{};
   a.X = x; a.Wp = reinterpret_cast<const u32x4*>(wp); a.winv = winv; a.bias = bias; a.Res = nullptr; a.Y = y;
   a.M = (int)M; a.N = Cout; a.K = taps * Cin; a.epi = GS_EPI_NONE;
   a.Cin = Cin; a.Cout = Cout; a.H = H; a.Wd = W; a.HW = H * W;
   a.tap0 = taps == 9 ? 0 : 4;
-  return gs_launch<XMODE>(a, st);
+  a.affine = affine;
+  return affine ? gs_launch<XMODE, true>(a, st) : gs_launch<XMODE>(a, st);
 }
 
 int conv3x3_f16x3_f32(const float* x, const void* wp, const float* winv, float* y, int T, int Cin, int Cout, int H, int W,
@@ -487,6 +538,14 @@ int conv3x3_nhwc_f16x3_f32(const float* x, const void* wp, const float* winv, fl
 int conv1x1_f16x3_f32(const float* x, const void* wp, const float* winv, const float* bias, float* y, int T, int Cin, int Cout, int H,
                       int W, hipStream_t st) {
   return gs_conv<1>(x, wp, winv, bias, y, T, Cin, Cout, H, W, 1, st);
+}
+
+// ... with the operand NCHW or channels last ([T, H, W, Cin]: two 16-byte loads where NCHW takes eight of 4 bytes; the same k order
+// and running row scale, so the same bits), and optionally relu(GroupNorm(x)) applied to it from its `affine` pairs.  y is NCHW.
+int conv1x1_fused_f16x3_f32(const float* x, int channels_last, const float* affine, const void* wp, const float* winv, const float* bias,
+                            float* y, int T, int Cin, int Cout, int H, int W, hipStream_t st) {
+  return channels_last ? gs_conv<2>(x, wp, winv, bias, y, T, Cin, Cout, H, W, 1, st, affine)
+                       : gs_conv<1>(x, wp, winv, bias, y, T, Cin, Cout, H, W, 1, st, affine);
 }
 
 }  // namespace univs

@@ -141,6 +141,14 @@ inline bool stream_linear_covered(long long M, int N, int K) {
 inline bool stream_conv_covered(long long M, int Cin, int Cout, int taps) {
   return (taps == 9 ? Cin % 128 == 0 : k_ring(Cin) != 0) && Cout % 16 == 0 && M >= 4096 && fits_int32(M, std::max(Cin, Cout));
 }
+// ... with the GroupNorm + ReLU of the operand folded into its load (a 1 x 1): the (scale, bias) pairs of two frames in LDS behind the
+// plan's bytes; the rows of one round of a workgroup must lie in at most two frames
+inline size_t gs_affine_lds(int Cin) { return (size_t)2 * Cin * 8; }
+inline bool stream_affine_covered(long long HW, int Cin) { return HW >= (GS_THREADS / 64) * GS_TILE_M && Cin <= 1024; }
+// ... and the instantiations that exist with it: up to four feature blocks per pass (they fit the register file with the pairs), and
+// the full pass of a Cin % 128 == 0 problem, eight blocks at ring 4 (the mask-feature convolution: no more spilled than without the
+// affine).  Five to seven blocks, and eight at ring 3, spill a few registers more with it: not built, the caller keeps the GroupNorm pass
+constexpr bool stream_affine_plan_covered(int RB, int ring) { return RB <= 4 || (RB == 8 && ring == 4); }
 struct StreamPlan {
   int RB, ring;                  // gemm_f16x3_stream<RB, ring, XMODE>
   unsigned gx, passes;

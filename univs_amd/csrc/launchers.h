@@ -64,6 +64,8 @@ int conv3x3_f16x3_f32(const float* x, const void* wp, const float* winv, float* 
                       hipStream_t st);
 int conv1x1_f16x3_f32(const float* x, const void* wp, const float* winv, const float* bias, float* y, int T, int Cin, int Cout, int H,
                       int W, hipStream_t st);
+int conv1x1_fused_f16x3_f32(const float* x, int channels_last, const float* affine, const void* wp, const float* winv, const float* bias,
+                            float* y, int T, int Cin, int Cout, int H, int W, hipStream_t st);
 
 // ---- gemm_f16x3_tile.hip: returns UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the shape or alignment is not covered, or the launch's error
 int linear_f16x3_tile_f32(const float* x, const void* wp, const float* winv, const float* bias, const float* residual, float* y,
@@ -81,11 +83,17 @@ int small_chain_f32(const float* x, int stages, const void* const* wp, const flo
 int small_linear_f32(const float* x, const float* xadd, const void* wp, const float* winv, const float* bias, int n_w, int f_off,
                      const float* residual, const float* ln_g, const float* ln_b, float ln_eps, float* y, long long M, int N, int K,
                      int relu, int add_features, int out_T, hipStream_t st);
+int small_linear_merged_f32(const float* ws, int plan, int L, int Nb, int Hh, const void* wp, const float* winv, const float* bias, int n_w,
+                            int f_off, const float* residual, const float* ln_g, const float* ln_b, float ln_eps, float* y, int N,
+                            hipStream_t st);
 
 // ---- cross_attn.hip: returns UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the shape or alignment is not covered, or the launch's error; cross_attention_workspace_floats: a count
 int cross_attention_f32(const float* q, const float* k, const float* v, const unsigned char* mask, const unsigned* row_flags,
                         unsigned generation, int L, int S, int N, int H, int hd, int ldq, int ldk, int ldv, float scale, float* ws,
                         float* out, hipStream_t st);
+int cross_attention_partials_f32(const float* q, const float* k, const float* v, const unsigned char* mask, const unsigned* row_flags,
+                                 unsigned generation, int L, int S, int N, int H, int hd, int ldq, int ldk, int ldv, float scale, float* ws,
+                                 int* plan_out, hipStream_t st);
 size_t cross_attention_workspace_floats(int L, int S, int N, int H);
 
 // ---- window_attn.hip: returns UNIVS_OK or the launch's error

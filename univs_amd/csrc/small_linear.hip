@@ -20,6 +20,7 @@
 #include "common.h"
 #include "f16x3.h"
 #include "launchers.h"
+#include "xattn_merge.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -46,6 +47,10 @@ struct SlArgs {
                                   // mask embeddings [Q', T, C] handed on as [T, Q', C] (...decoder_univs.py:527) without a copy of its own
   int add_features;               // Xadd applies to output features < add_features only (a multiple of 32; 0: to all) -- q, k = in_proj(tgt +
                                   // pos) and v = in_proj(tgt) of a self-attention in one launch
+  // MERGE: the operand is the attention output [L, Nb, 32 Hh] (row = q * Nb + n), never written: a slot's eight values are merged from
+  // the key segments' partials in `ws` (cross_attn.hip: [chunk][Nb * Hh][nseg][Lp][XA_PART]) while the tile is staged; X is unused
+  const float* ws;
+  int nseg, Lp, Nb, Hh;
 };
 
 typedef unsigned sl_u2 __attribute__((ext_vector_type(2)));
@@ -56,7 +61,8 @@ __device__ __forceinline__ float sl_row_sum(float v) {          // over the four
   return __uint_as_float(s2.x) + __uint_as_float(s2.y);
 }
 
-__global__ __launch_bounds__(64 * SL_WAVES, 3) void small_linear_kernel(const SlArgs a) {
+template <bool MERGE>
+__global__ __launch_bounds__(64 * SL_WAVES, MERGE ? 2 : 3) void small_linear_kernel(const SlArgs a) {
   // LDS: operand tiles [tile: with x_add / plain][part h, m][k-step][lane] 16-byte units | row maxima [2][16] | inverse scales [2][16]
   extern __shared__ __attribute__((aligned(16))) u32x4 xs[];
   __shared__ float red[2][SL_WAVES][16];
@@ -104,8 +110,20 @@ __global__ __launch_bounds__(64 * SL_WAVES, 3) void small_linear_kernel(const Sl
     if (s_ < KS * 64) {
       const int ks = s_ >> 6, l_ = s_ & 63, j_ = l_ & 15, g_ = l_ >> 4;
       const long long off = (long long)min(row0 + j_, M - 1) * K + 32 * ks + 8 * g_;
-      xv[i][0] = *reinterpret_cast<const f32x4*>(a.X + off);
-      xv[i][1] = *reinterpret_cast<const f32x4*>(a.X + off + 4);
+      if constexpr (MERGE) {
+        // row r = (query q, batch entry n), k-step = head, k-group = channels 8 g_ ...: rows past M repeat the last row, rows q >= L
+        // of a chunk are never read
+        const int r = min(row0 + j_, M - 1), q = r / a.Nb, n = r - q * a.Nb;
+        const int chunk = q / a.Lp, ql = q - chunk * a.Lp;
+        const float* base = a.ws + ((((long long)chunk * a.Nb * a.Hh + (n * a.Hh + ks)) * a.nseg) * a.Lp + ql) * XA_PART;
+        float mv[8];
+        xa_merge_partials<8>(base, (long long)a.Lp * XA_PART, a.nseg, 8 * g_, mv);
+        xv[i][0] = (f32x4){mv[0], mv[1], mv[2], mv[3]};
+        xv[i][1] = (f32x4){mv[4], mv[5], mv[6], mv[7]};
+      } else {
+        xv[i][0] = *reinterpret_cast<const f32x4*>(a.X + off);
+        xv[i][1] = *reinterpret_cast<const f32x4*>(a.X + off + 4);
+      }
       if (need_add) {
         xw[i][0] = xv[i][0] + *reinterpret_cast<const f32x4*>(a.Xadd + off);
         xw[i][1] = xv[i][1] + *reinterpret_cast<const f32x4*>(a.Xadd + off + 4);
@@ -251,8 +269,33 @@ int small_linear_f32(const float* x, const float* xadd, const void* wp, const fl
   a.M = (int)M; a.N = N; a.K = K; a.Nw = n_w; a.f_off = f_off; a.relu = relu ? 1 : 0; a.add_features = add_features; a.out_T = out_T;
   dim3 grid((unsigned)((M + 15) / 16), (unsigned)((N + 32 * SL_WAVES - 1) / (32 * SL_WAVES)));
   const size_t lds = (size_t)2 * 2 * (K / 32) * 64 * 16;        // two operand tiles (x + x_add, x), two parts each
-  hipLaunchKernelGGL(small_linear_kernel, grid, dim3(64 * SL_WAVES), lds, st, a);
+  hipLaunchKernelGGL(small_linear_kernel<false>, grid, dim3(64 * SL_WAVES), lds, st, a);
   return check_launch("small_linear_f32");
+}
+
+// The same Linear on the attention output [L, Nb, 32 Hh] that is merged from the partials in `ws` while the operand tile is staged
+// (`plan` = segments + 65536 x query blocks per wave, as cross_attention_partials_f32 reported it): no xattn_merge launch, no
+// [L, Nb, E] tensor.  Bit-identical to small_linear_f32 on xattn_merge's output.  Returns as small_linear_f32.
+int small_linear_merged_f32(const float* ws, int plan, int L, int Nb, int Hh, const void* wp, const float* winv, const float* bias, int n_w,
+                            int f_off, const float* residual, const float* ln_g, const float* ln_b, float ln_eps, float* y, int N,
+                            hipStream_t st) {
+  const long long M = (long long)L * Nb;
+  if (M <= 0 || N <= 0) return UNIVS_OK;
+  auto mis = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+  const int nseg = plan & 0xffff, nqb = plan >> 16, K = 32 * Hh;
+  if (nseg < 1 || nqb < 1 || nqb > 7 || Hh < 1 || K > SL_KMAX || N % 16 != 0 || n_w % 4 != 0 || f_off % 4 != 0 || f_off < 0 || f_off + N > n_w ||
+      M > 16LL * 65535 || (ln_g && N != 32 * SL_WAVES) || (ln_b && !ln_g) || (reinterpret_cast<uintptr_t>(ws) & 7) || mis(wp) || mis(winv) ||
+      mis(bias) || mis(residual) || mis(ln_g) || mis(ln_b) || mis(y) || M * (long long)std::max(N, K) * 4 >= 0x7FFFFFFFLL)
+    return UNIVS_ERR_NOT_IMPLEMENTED;
+  SlArgs a{};
+  a.X = nullptr; a.Xadd = nullptr; a.Wp = reinterpret_cast<const u32x4*>(wp); a.winv = winv; a.bias = bias; a.Res = residual;
+  a.ln_g = ln_g; a.ln_b = ln_b; a.ln_eps = ln_eps; a.Y = y;
+  a.M = (int)M; a.N = N; a.K = K; a.Nw = n_w; a.f_off = f_off; a.relu = 0; a.add_features = 0; a.out_T = 0;
+  a.ws = ws; a.nseg = nseg; a.Lp = 16 * nqb; a.Nb = Nb; a.Hh = Hh;
+  dim3 grid((unsigned)((M + 15) / 16), (unsigned)((N + 32 * SL_WAVES - 1) / (32 * SL_WAVES)));
+  const size_t lds = (size_t)2 * 2 * (K / 32) * 64 * 16;
+  hipLaunchKernelGGL(small_linear_kernel<true>, grid, dim3(64 * SL_WAVES), lds, st, a);
+  return check_launch("small_linear_merged_f32");
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------

@@ -20,6 +20,7 @@ Python loop of the reference's new-entity test (:640-645) is one batched mask-Io
 Sub-tasks: 'vis' / 'entity_vis_*' (instance-style), 'vps' (panoptic: things + stuff, segment ids remembered in
 `targets[0]`) and 'vss' (semantic: per-clip class x mask maps, no entity bookkeeping).
 """
+import contextlib
 import math
 from typing import Tuple
 
@@ -233,7 +234,9 @@ def window_features_on_owner(model, x, frames, shard):
     if not mine:
         return {}, None
     feats = model.backbone(x[mine] if mine != list(range(mine[0], mine[0] + len(mine))) else x[mine[0]:mine[0] + len(mine)])
-    mf, bfe, _enc, ms = model.sem_seg_head.pixel_decoder.forward_features(feats)
+    pd = model.sem_seg_head.pixel_decoder
+    with getattr(pd, "normed_optional", contextlib.nullcontext)():      # (the predictor ignores `bfe`: it may be None)
+        mf, bfe, _enc, ms = pd.forward_features(feats)
     return {f: k for k, f in enumerate(mine)}, (mf, bfe, list(ms))
 
 
@@ -534,7 +537,8 @@ class InferenceVideoEntity(nn.Module):
                     head = model.sem_seg_head
                     if (self.pixel_decoder_once_per_window and self.num_frames_window_test > T and stride < T
                             and hasattr(head, "pixel_decoder") and hasattr(head, "predictor")):
-                        mf, bfe, _enc, ms = head.pixel_decoder.forward_features(feats_window)
+                        with getattr(head.pixel_decoder, "normed_optional", contextlib.nullcontext)():
+                            mf, bfe, _enc, ms = head.pixel_decoder.forward_features(feats_window)
                         win_pd = (mf, bfe, list(ms))
                 o = i - win_start
                 if win_pd is not None:

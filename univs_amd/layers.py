@@ -58,14 +58,6 @@ class Conv2d(nn.Conv2d):
     def convolve(self, x):
         """the convolution alone (no norm, no activation): for callers that fuse the norm into their next step"""
         y = None
-        if (SWITCHES.split_conv and x.is_cuda and self.kernel_size == (1, 1) and self.stride == (1, 1) and self.padding == (0, 0)
-                and self.dilation == (1, 1) and self.groups == 1):
-            from . import ops
-            y = ops.conv1x1(x, self.weight, self.bias)
-        return y if y is not None else F.conv2d(x, self.weight, self.bias, self.stride, self.padding, self.dilation, self.groups)
-
-    def forward(self, x):
-        y = None
         if (SWITCHES.split_conv and x.is_cuda and self.bias is None and self.kernel_size == (3, 3) and self.stride == (1, 1)
                 and self.padding == (1, 1) and self.dilation == (1, 1) and self.groups == 1):
             from . import ops
@@ -74,7 +66,10 @@ class Conv2d(nn.Conv2d):
               and self.dilation == (1, 1) and self.groups == 1):
             from . import ops
             y = ops.conv1x1(x, self.weight, self.bias)   # bias in the epilogue; None when not covered
-        x = y if y is not None else F.conv2d(x, self.weight, self.bias, self.stride, self.padding, self.dilation, self.groups)
+        return y if y is not None else F.conv2d(x, self.weight, self.bias, self.stride, self.padding, self.dilation, self.groups)
+
+    def forward(self, x):
+        x = self.convolve(x)
         if isinstance(self.norm, nn.GroupNorm) and x.dtype == torch.float32:
             # GroupNorm (+ ReLU) epilogue through the HIP operator; the module only holds the parameters
             from . import ops
@@ -234,6 +229,14 @@ class MultiheadAttention(nn.Module):
                     m3 = ops.pad4_mask(attn_mask)                # (cached per mask object: one padded copy for all layers)
                 if m3.dim() == 2:
                     m3 = m3.view(1, L, m3.shape[-1])
+            if SWITCHES.fold_attn_merge and _small(q, self.out_proj.weight, self.out_proj.bias):
+                # ... and the merge of the key segments inside the out-projection's kernel (few rows, K = E <= 256): two launches, the
+                # [L, N, E] attention output is never written; bit-identical to the three launches below
+                from . import fused_ops
+                tail = dict(residual=residual, ln=(norm.weight, norm.bias, norm.eps)) if norm is not None else {}
+                y = fused_ops.attention_out_proj(q, k, v, m3, h, 1.0 / math.sqrt(d), self.out_proj.weight, self.out_proj.bias, **tail)
+                if y is not None:
+                    return (y if norm is not None or residual is None else residual + y), None
             out = ops.cross_attention(q, k, v, m3, h, 1.0 / math.sqrt(d))
             if out is not None:
                 return project(out), None

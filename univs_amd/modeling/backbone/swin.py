@@ -389,7 +389,12 @@ class SwinTransformer(nn.Module):
                 (x_out, H, W, x, Wh, Ww), x_normed = self.layers[i](x, Wh, Ww), None
             if i in self.out_indices:
                 x_out = x_normed if x_normed is not None else layer_norm(getattr(self, f"norm{i}"), x_out)
-                # tokens -> NCHW (swin.py:676-683 permute + contiguous): an LDS tile transpose on the GPU
+                if SWITCHES.swin_channels_last and x_out.is_cuda and not torch.is_grad_enabled() and x_out.is_contiguous():
+                    # tokens -> NCHW (swin.py:676-683 permute + contiguous) WITHOUT the copy: the same shape and values as a channels-last
+                    # view of the tokens; the pixel decoder's 1 x 1 convolutions read it where it lies (fused_ops.conv1x1_fused)
+                    outs[f"res{i + 2}"] = x_out.view(-1, H, W, self.num_features[i]).permute(0, 3, 1, 2)
+                    continue
+                # ... with the copy: an LDS tile transpose on the GPU
                 outs[f"res{i + 2}"] = ops.transpose_last2(x_out).view(-1, self.num_features[i], H, W)
         return outs
 

@@ -83,8 +83,8 @@ class MaskFormerHead(nn.Module):
         if targets is not None and hasattr(self.predictor, "prefetch_prompts"):
             # the annotation-only part of the visual-prompt sampler, on a side stream, ahead of the pixel decoder
             self.predictor.prefetch_prompts(targets, next(iter(features.values())).shape[0])
-        mask_features, mask_features_bfe_conv, enc_features, multi_scale_features = \
-            self.pixel_decoder.forward_features(features)
+        with self.pixel_decoder.normed_optional():          # (the predictor ignores mask_features_bfe_conv: it may be None)
+            mask_features, mask_features_bfe_conv, enc_features, multi_scale_features = self.pixel_decoder.forward_features(features)
         if self.transformer_in_feature != "multi_scale_pixel_decoder":
             raise ValueError("only TRANSFORMER_IN_FEATURE='multi_scale_pixel_decoder' is on the hot path")
         return self.predictor(multi_scale_features, mask_features, mask_features_bfe_conv, mask, targets)

@@ -15,6 +15,7 @@ work is organised (results are the same):
     msdeformattn.py:62) are dropped: valid_ratio is identically 1;
   * everything stays fp32 regardless of autocast (msdeformattn.py:316,322).
 """
+import contextlib
 from typing import Callable, Dict, List, Optional, Union
 
 import numpy as np
@@ -22,7 +23,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ... import ops
+from ... import fused_ops, ops
 from ...layers import Conv2d, get_activation_fn, get_norm, layer_norm, linear, linear_act
 from ...registry import SEM_SEG_HEADS_REGISTRY, ShapeSpec, configurable
 from ..position_encoding import PositionEmbeddingSine
@@ -375,7 +376,23 @@ class MSDeformAttnPixelDecoder(nn.Module):
             self._pe_cache[key] = p
         return p
 
+    @contextlib.contextmanager
+    def normed_optional(self):
+        """Inside the block `forward_features(features)` may return None as its second element: for the callers that hand it to a
+        predictor which ignores it (MaskFormerHead.layers, inference/video_entity.py).  The mask-feature convolution then normalises
+        its operand while loading it (SWITCHES.fold_fpn_norm) and the normalised tensor is never written.  The call itself keeps its
+        one-argument form: drop-in callers and wrappers of it are not concerned."""
+        old = self.__dict__.get("_normed_optional", False)
+        self.__dict__["_normed_optional"] = True
+        try:
+            yield self
+        finally:
+            self.__dict__["_normed_optional"] = old
+
     def forward_features(self, features):
+        """(mask_features, the normalised FPN output they are computed from, the coarsest encoder level, multi_scale_features); the
+        second is the correct tensor, or None inside `normed_optional()` -- never anything else."""
+        want_normed = not self.__dict__.get("_normed_optional", False)
         with torch.autocast(device_type=next(iter(features.values())).device.type, enabled=False):
             if SWITCHES.graphs and not self.training and all(f.is_cuda for f in features.values()):
                 # hipGraph replay per input signature (univs_amd/graphs.py): one launch instead of ~200
@@ -383,8 +400,25 @@ class MSDeformAttnPixelDecoder(nn.Module):
                 if g is None:
                     from ...graphs import GraphedCallable
                     g = self.__dict__["_graphed"] = GraphedCallable(self._forward_features)
-                return g({k: features[k] for k in self.in_features})
-            return self._forward_features(features)
+                return g({k: features[k] for k in self.in_features}, bool(want_normed))
+            return self._forward_features(features, want_normed)
+
+    @staticmethod
+    def _conv1x1_in_place(conv, x):
+        """The 1 x 1 convolution `conv` (no norm, no activation) of a backbone feature that is a channels-last VIEW of its token tensor
+        (SwinTransformer, SWITCHES.swin_channels_last), read where it lies -> (y NCHW or None, x).  Where the kernel does not cover the
+        call, x comes back as the contiguous NCHW tensor the other paths take, made by the LDS tile transpose: handed on as the view it
+        would be copied by ATen's generic strided kernel at the first `.contiguous()` (0.6 TB/s)."""
+        if not x.is_cuda or x.is_contiguous() or not x.is_contiguous(memory_format=torch.channels_last):
+            return None, x
+        y = None
+        if SWITCHES.split_conv and x.dtype == torch.float32 and not ops.needs_grad(x, conv.weight, conv.bias):
+            y = fused_ops.conv1x1_fused(x, conv.weight, conv.bias)
+        if y is None:
+            T, C, H, W = x.shape
+            tokens = x.permute(0, 2, 3, 1).reshape(T, H * W, C)       # (a view: x is channels last)
+            x = ops.transpose_last2(tokens).view(T, C, H, W) if not ops.needs_grad(x) else x.contiguous()
+        return y, x
 
     def _input_proj(self, idx, x):
         """input_proj[idx] = Sequential(Conv2d 1 x 1, GroupNorm(32)) (msdeformattn.py:205-212) through the HIP operators (the
@@ -397,15 +431,17 @@ class MSDeformAttnPixelDecoder(nn.Module):
             return ops.group_norm(y, gn.num_groups, gn.weight, gn.bias, gn.eps)
         return self.input_proj[idx](x)
 
-    def _forward_features(self, features):
+    def _forward_features(self, features, want_normed=True):
         srcs, pos, affines = [], [], []
         for idx, f in enumerate(self.transformer_in_features[::-1]):
             x = features[f].float()
             conv, gn = self.input_proj[idx][0], self.input_proj[idx][1]
+            raw, x = self._conv1x1_in_place(conv, x)
             if x.is_cuda and not torch.is_grad_enabled() and not ops.needs_grad(x, conv.weight):
                 # the convolution alone + its GroupNorm in affine form: the normalisation is applied where the level is written into
                 # the encoder input (ops.tokens_from_nchw), not by a pass of its own
-                raw = ops.conv1x1(x, conv.weight, conv.bias) if SWITCHES.split_conv else None
+                if raw is None:
+                    raw = ops.conv1x1(x, conv.weight, conv.bias) if SWITCHES.split_conv else None
                 raw = conv(x) if raw is None else raw
                 srcs.append(raw)
                 affines.append(ops.group_norm_affine(raw, gn.num_groups, gn.weight, gn.bias, gn.eps))
@@ -426,15 +462,17 @@ class MSDeformAttnPixelDecoder(nn.Module):
             out = [ops.transpose_last2(z).view(bs, -1, spatial_shapes[i][0], spatial_shapes[i][1]) for i, z in enumerate(y)]   # (a row range: no copy)
         else:
             out = [z.transpose(1, 2).reshape(bs, -1, spatial_shapes[i][0], spatial_shapes[i][1]) for i, z in enumerate(y)]
+        normed, folded = None, None
         for idx, f in enumerate(self.in_features[:self.num_fpn_levels][::-1]):
             x = features[f].float()
             lat = self.lateral_convs[idx]
             y_ = None
+            raw_in_place, x = self._conv1x1_in_place(lat, x)
             if (x.is_cuda and isinstance(lat.norm, nn.GroupNorm) and lat.activation is None and not torch.is_grad_enabled()
                     and x.shape[-2] == 2 * out[-1].shape[-2] and x.shape[-1] == 2 * out[-1].shape[-1]):
                 # lateral 1 x 1 convolution, GroupNorm statistics, then `GroupNorm(lateral) + upsample(coarser)` in one pass that
                 # normalises the convolution output while reading it (csrc/resample.hip: upsample2x_add_kernel)
-                raw = lat.convolve(x)
+                raw = raw_in_place if raw_in_place is not None else lat.convolve(x)
                 y_ = ops.upsample2x_add(out[-1], raw, ops.group_norm_affine(raw, lat.norm.num_groups, lat.norm.weight, lat.norm.bias,
                                                                           lat.norm.eps))
                 if y_ is None:
@@ -443,6 +481,22 @@ class MSDeformAttnPixelDecoder(nn.Module):
             if y_ is None:
                 cur_fpn = lat(x)
                 y_ = ops.bilinear_resample(out[-1], cur_fpn.shape[-2:], addend=cur_fpn)
-            out.append(self.output_convs[idx](y_))
+            oc = self.output_convs[idx]
+            if (idx + 1 == self.num_fpn_levels and not want_normed and SWITCHES.fold_fpn_norm and SWITCHES.split_conv and y_.is_cuda
+                    and y_.dtype == torch.float32 and len(out) >= self.maskformer_num_feature_levels
+                    and isinstance(oc.norm, nn.GroupNorm) and oc.activation is F.relu and not torch.is_grad_enabled()
+                    and self.mask_features.norm is None and self.mask_features.activation is None):
+                # the last FPN level, whose normalised output only the mask-feature convolution reads: the 3 x 3 convolution alone, its
+                # GroupNorm as per-plane (scale, bias), and the 1 x 1 applies relu(fma(x, scale, bias)) while it loads x
+                raw = oc.convolve(y_)
+                affine = ops.group_norm_affine(raw, oc.norm.num_groups, oc.norm.weight, oc.norm.bias, oc.norm.eps)
+                folded = fused_ops.conv1x1_fused(raw, self.mask_features.weight, self.mask_features.bias, affine)
+                if folded is None:                         # (not covered: the pass of its own)
+                    normed = ops.group_norm(raw, oc.norm.num_groups, oc.norm.weight, oc.norm.bias, oc.norm.eps, relu=True)
+                out.append(normed)                         # (None when folded: nothing below reads out[-1])
+                continue
+            out.append(oc(y_))
         multi_scale_features = out[:self.maskformer_num_feature_levels]
+        if folded is not None:
+            return folded, None, out[0], multi_scale_features
         return self.mask_features(out[-1]), out[-1], out[0], multi_scale_features

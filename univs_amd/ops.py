@@ -980,14 +980,10 @@ def pad4_mask(mask):
     return padded
 
 
-def cross_attention(q, k, v, mask, num_heads, scale):
-    """softmax(scale q k^T, masked) v per (batch entry, head) in one pass over the keys (include/univs_hip.h:
-    univs_cross_attention_f32; csrc/cross_attn.hip): the attention core of nn.MultiheadAttention as the decoder's
-    CrossAttentionLayer uses it (transformer_layers.py:95-115) between the in- and out-projections.
-    q [L, N, E], k / v [S, N, E] sequence-first float32 (E = num_heads * 32), dense or column slices of wider projections; mask
-    bool / uint8 [N, L, S] (True = masked out, shared by the heads), a `DeferredMask` of that shape, or None.
-    Returns [L, N, E], or None when not covered."""
-    _inference_only("cross_attention", q, k, v)
+def _cross_attention_args(q, k, v, mask, num_heads):
+    """The prologue of `cross_attention` (and of fused_ops.attention_out_proj, the same core without its merge launch): the operands as
+    the kernel takes them -- (q, k, v, mask bytes or None, row flags or None, generation, L, S, N, H, ldq, ldk, ldv) -- or None when
+    the call is not covered."""
     if not (q.is_cuda and q.dtype == torch.float32 and k.dtype == torch.float32 and v.dtype == torch.float32):
         return None
     L, N, E = q.shape
@@ -1016,9 +1012,24 @@ def cross_attention(q, k, v, mask, num_heads, scale):
             ld = E
         lds_.append((t, ld))
     (q, ldq), (k, ldk), (v, ldv) = lds_
+    return q, k, v, mask, flags, gen, L, S, N, H, ldq, ldk, ldv
+
+
+def cross_attention(q, k, v, mask, num_heads, scale):
+    """softmax(scale q k^T, masked) v per (batch entry, head) in one pass over the keys (include/univs_hip.h:
+    univs_cross_attention_f32; csrc/cross_attn.hip): the attention core of nn.MultiheadAttention as the decoder's
+    CrossAttentionLayer uses it (transformer_layers.py:95-115) between the in- and out-projections.
+    q [L, N, E], k / v [S, N, E] sequence-first float32 (E = num_heads * 32), dense or column slices of wider projections; mask
+    bool / uint8 [N, L, S] (True = masked out, shared by the heads), a `DeferredMask` of that shape, or None.
+    Returns [L, N, E], or None when not covered."""
+    _inference_only("cross_attention", q, k, v)
+    args = _cross_attention_args(q, k, v, mask, num_heads)
+    if args is None:
+        return None
+    q, k, v, mask, flags, gen, L, S, N, H, ldq, ldk, ldv = args
     lib = _lib.load()
     ws = torch.empty(int(lib.univs_cross_attention_workspace(L, S, N, H)), dtype=torch.float32, device=q.device)
-    out = torch.empty((L, N, E), dtype=torch.float32, device=q.device)
+    out = torch.empty((L, N, H * 32), dtype=torch.float32, device=q.device)
     ok = _call("cross_attention", lib.univs_cross_attention_flagged_f32, q, _ptr(q), _ptr(k), _ptr(v), _opt(mask), _opt(flags), gen,
                L, S, N, H, 32, ldq, ldk, ldv, float(scale), _ptr(ws), _ptr(out))
     return out if ok else None

@@ -77,6 +77,18 @@ class Switches:
     sampler: str = "auto"
     # hipGraph replay of the static parts of a clip (backbone, pixel decoder): see univs_amd/graphs.py
     graphs: bool = False
+    # the GroupNorm + ReLU behind the FPN output convolution applied by the mask-feature 1 x 1 convolution while it loads its operand
+    # (fused_ops.conv1x1_fused with the affine pairs) where nobody else reads the normalised tensor; False: a pass of its own
+    fold_fpn_norm: bool = True
+    # the attention core's merge of its key segments inside the out-projection that follows it (fused_ops.attention_out_proj: few rows,
+    # E <= 256 -- the decoder's cross- and self-attention layers); False: a merge launch and an [L, N, E] tensor of its own.
+    # OFF by default: measured slower -- the 18 out-projections of a clip go from 9.1 to 24.8 us each (+0.28 ms) where the merge launches
+    # they replace took 0.15 ms: 32 workgroups walk the segments one after the other where xattn_merge spreads them over 128 000 threads
+    # (profiles/seam_fold_clip_breakdown_this.txt); bit-identical either way
+    fold_attn_merge: bool = False
+    # Swin stage outputs handed on as channels-last VIEWS of the token tensors (same shape and values as the NCHW copy); the pixel
+    # decoder's 1 x 1 convolutions read them in place (fused_ops.conv1x1_fused); False: an LDS tile transpose per stage
+    swin_channels_last: bool = True
 
 
 SWITCHES = Switches(
@@ -87,7 +99,8 @@ SWITCHES = Switches(
     presplit_kmin=int(os.environ.get("UNIVS_PRESPLIT_KMIN", "768")), fused_mlp=_flag("UNIVS_FUSED_MLP", True),
     fused_cross_attention=_flag("UNIVS_FUSED_XATTN", True), fused_norm1=_flag("UNIVS_FUSED_NORM1", True), small_linear=_flag("UNIVS_SMALL_LINEAR", True),
     resident_presplit=_flag("UNIVS_RESIDENT_PRESPLIT", True), small_mlp_chain=_flag("UNIVS_SMALL_MLP_CHAIN", True), fused_proca=_flag("UNIVS_FUSED_PROCA", True),
-    fused_sampler=_flag("UNIVS_FUSED_SAMPLER", True), small_mlp_norm=_flag("UNIVS_SMALL_MLP_NORM", True))
+    fused_sampler=_flag("UNIVS_FUSED_SAMPLER", True), small_mlp_norm=_flag("UNIVS_SMALL_MLP_NORM", True),
+    fold_fpn_norm=_flag("UNIVS_FOLD_FPN_NORM", True), fold_attn_merge=_flag("UNIVS_FOLD_ATTN_MERGE", False), swin_channels_last=_flag("UNIVS_SWIN_CHANNELS_LAST", True))
 if SWITCHES.sampler not in ("auto", "reference", "device"):
     raise ValueError(f"UNIVS_SAMPLER={SWITCHES.sampler!r} (expected 'auto', 'reference' or 'device')")
 
