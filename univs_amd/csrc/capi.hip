@@ -7,6 +7,7 @@
 
 #include "../../include/univs_eval_hip.h"
 #include "../../include/univs_fused_hip.h"
+#include "../../include/univs_pvos_hip.h"
 #include "common.h"
 #include "config.h"
 #include "launchers.h"
@@ -883,6 +884,15 @@ int univs_vis_overlap_counts(const int32_t* dt_bounds, const int32_t* dt_starts,
   if (!dt_bounds || !dt_starts || !gt_bounds || !gt_ones || !gt_starts || !inter) return e.null_pointer();
   return e.covered(vis_overlap_counts(dt_bounds, dt_starts, gt_bounds, gt_ones, gt_starts, D, G, T, H, W, gt_max_bounds, inter, e.st),
                    "not covered (H W < 2^31, T <= 65535, at most 16384 boundaries per ground-truth mask: 128 KB of LDS)");
+}
+
+// (include/univs_pvos_hip.h)
+int univs_pvos_counts(const uint8_t* gt, const uint8_t* pred, int T, int H, int W, int d, int K, int32_t* counts, void* stream) {
+  const Entry e("univs_pvos_counts", stream);
+  if (T < 1 || H < 1 || W < 1 || d < 1 || K < 1)                  // (beyond the kernel's sizes: "not covered")
+    return e.invalid("bad arguments T=%d H=%d W=%d d=%d K=%d", T, H, W, d, K);
+  if (!gt || !pred || !counts) return e.null_pointer();
+  return e.covered(pvos_counts(gt, pred, T, H, W, d, K, counts, e.st), "not covered (d <= 88, K <= 255, T H W < 2^31)");
 }
 
 // The two window-attention entries on image-layout operands share their checks

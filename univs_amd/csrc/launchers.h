@@ -206,4 +206,7 @@ int davis_counts(const unsigned char* gt, const unsigned char* pred, int T, int 
 int vis_overlap_counts(const int* dt_bounds, const int* dt_starts, const int* gt_bounds, const int* gt_ones, const int* gt_starts, int D,
                        int G, int T, int H, int W, int gt_max_bounds, int* inter, hipStream_t st);
 
+// ---- pvos_count.hip: returns UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the sizes are not covered, or the launch's error
+int pvos_counts(const unsigned char* gt, const unsigned char* pred, int T, int H, int W, int d, int K, int* counts, hipStream_t st);
+
 }  // namespace univs

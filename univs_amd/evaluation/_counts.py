@@ -5,7 +5,8 @@
     launch(name, "univs_...", gt, outputs, ...)
 
 and its module's `*_counts` is `kernel_else_aten`.  The kernels are csrc/pair_count.hip, vss_count.hip and davis_count.hip over
-csrc/count_core.h; the contract of all three wrappers is pinned in tests/test_eval_counts_contract_cpu.py.
+csrc/count_core.h; the contract of all three wrappers is pinned in tests/test_eval_counts_contract_cpu.py.  pvos_counts.py
+(csrc/pvos_count.hip) is written over the same three steps; tests/test_pvos_eval_cpu.py pins its contract.
 """
 import numpy as np
 import torch
