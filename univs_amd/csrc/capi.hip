@@ -8,6 +8,7 @@
 #include "../../include/univs_eval_hip.h"
 #include "../../include/univs_fused_hip.h"
 #include "../../include/univs_pvos_hip.h"
+#include "../../include/univs_semantic_hip.h"
 #include "common.h"
 #include "config.h"
 #include "launchers.h"
@@ -893,6 +894,18 @@ int univs_pvos_counts(const uint8_t* gt, const uint8_t* pred, int T, int H, int 
     return e.invalid("bad arguments T=%d H=%d W=%d d=%d K=%d", T, H, W, d, K);
   if (!gt || !pred || !counts) return e.null_pointer();
   return e.covered(pvos_counts(gt, pred, T, H, W, d, K, counts, e.st), "not covered (d <= 88, K <= 255, T H W < 2^31)");
+}
+
+// (include/univs_semantic_hip.h)
+int univs_semantic_quality_counts_f32(const float* mask_embed, const float* features, int T, int N, int C, int HW, int t_step, float t_hi,
+                                      float t_lo, int32_t* counts, void* stream) {
+  const Entry e("univs_semantic_quality_counts_f32", stream);
+  if (T < 1 || N < 1 || C < 1 || HW < 1 || t_step < 1)            // (beyond the kernel's sizes: "not covered")
+    return e.invalid("bad arguments T=%d N=%d C=%d HW=%d t_step=%d", T, N, C, HW, t_step);
+  if (!mask_embed || !features || !counts) return e.null_pointer();
+  return e.covered(semantic_quality_counts_f32(mask_embed, features, T, N, C, HW, t_step, t_hi, t_lo, counts, e.st),
+                   "not covered (ceil(T / t_step) HW < 2^31, C HW 4 < 2^31, ceil(T / t_step) <= 65535, N <= 2097120, C <= 315, or up to "
+                   "1239 where few rows make a smaller LDS tile)");
 }
 
 // The two window-attention entries on image-layout operands share their checks

@@ -209,4 +209,8 @@ int vis_overlap_counts(const int* dt_bounds, const int* dt_starts, const int* gt
 // ---- pvos_count.hip: returns UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the sizes are not covered, or the launch's error
 int pvos_counts(const unsigned char* gt, const unsigned char* pred, int T, int H, int W, int d, int K, int* counts, hipStream_t st);
 
+// ---- semantic_decode.hip: returns UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the sizes are not covered, or the launch's error
+int semantic_quality_counts_f32(const float* mask_embed, const float* features, int T, int N, int C, int HW, int t_step, float t_hi,
+                                float t_lo, int* counts, hipStream_t st);
+
 }  // namespace univs
