@@ -5,6 +5,7 @@
 
 #include <mutex>
 
+#include "../../include/univs_encoder_hip.h"
 #include "../../include/univs_eval_hip.h"
 #include "../../include/univs_fused_hip.h"
 #include "../../include/univs_pvos_hip.h"
@@ -309,6 +310,21 @@ int univs_linear_blocked_presplit_f32(const float* x, const void* wp, const floa
     return linear_split_f32(x, static_cast<const float*>(wp), bias, nullptr, y, M, N, K, /*LS_EPI_BLOCKED=*/4, e.st, rows_per_batch, col_block,
                             winv);
   });
+}
+
+int univs_encoder_linear_pair_presplit_f32(const float* x, const float* add, long long add_rows, const void* wp_a, const float* winv_a,
+                                           const float* bias_a, int N_a, int col_block_a, float* y_a, const void* wp_b,
+                                           const float* winv_b, const float* bias_b, int N_b, int col_block_b, float* y_b, long long M,
+                                           int K, long long rows_per_batch, void* stream) {
+  const Entry e("univs_encoder_linear_pair_presplit_f32", stream);
+  if (M < 1 || N_a < 1 || N_b < 1 || K < 1 || add_rows < 1 || rows_per_batch < 1 || col_block_a < 1 || col_block_b < 1)
+    return e.invalid("bad arguments M=%lld K=%d add_rows=%lld rows_per_batch=%lld N_a=%d col_block_a=%d N_b=%d col_block_b=%d", M, K, add_rows,
+                     rows_per_batch, N_a, col_block_a, N_b, col_block_b);
+  if (!x || !add || !wp_a || !winv_a || !y_a || !wp_b || !winv_b || !y_b) return e.null_pointer();
+  return e.launched(linear_pair_f16x3_f32(x, add, add_rows, wp_a, winv_a, bias_a, N_a, col_block_a, y_a, wp_b, winv_b, bias_b, N_b, col_block_b,
+                                          y_b, M, K, rows_per_batch, e.st),
+                    "not covered (K == 256, add_rows == rows_per_batch dividing M, N_a in passes of 113 .. 128 features and N_b of 81 .. 96, "
+                    "column blocks of a multiple of 4 dividing N, 16-byte aligned pointers, M max(K, N_a, N_b) 4 < 2^31)");
 }
 
 int univs_conv3x3_presplit_f32(const float* x, const void* wp, const float* winv, int T, int Cin, int Cout, int H, int W,

@@ -133,6 +133,49 @@ inline ResidentPlan plan_f16x3_resident(long long M, int N, int K, bool presplit
   return p;
 }
 
+// ---- two W-resident Linears on one stream of x (linear_pair_f16x3.hip): A on x, B on x + add[row % add_rows], both column-blocked
+// and on the split image.  The passes of both problems share the grid's y: A's first, then B's; each problem's passes are the ones
+// plan_f16x3_resident gives it alone (same cap, same rounding), the row ranges are dealt for the sum.  No lower bound on M: the
+// staging of W is paid once for two Linears, and the launch replaces a pass over x that costs more than it at any size.
+inline bool pair_covered(long long M, int N_a, int N_b, int K, long long add_rows, long long blk_rows, int blk_cols_a, int blk_cols_b) {
+  if (M < 1 || N_a < 1 || N_b < 1 || add_rows < 1 || blk_rows < 1 || add_rows != blk_rows || M % add_rows != 0) return false;
+  if (K != 256) return false;                              // the blocked epilogue's K (resident_covered)
+  if (!fits_int32(M, std::max(K, std::max(N_a, N_b)))) return false;   // (add_rows <= M: the table fits with x)
+  return blocked_ok(M, N_a, (int)blk_rows, blk_cols_a) && blocked_ok(M, N_b, (int)blk_rows, blk_cols_b);
+}
+struct PairPlan {
+  bool covered;
+  int RB[2], ring;               // linear_pair_f16x3<RB of A, RB of B, ring>
+  unsigned gx, passes[2];        // grid: gx x (passes[0] + passes[1])
+  size_t lds;                    // the larger of the two slabs
+  int rows_per_pass[2];
+};
+inline PairPlan plan_f16x3_pair(long long M, int N_a, int N_b, int K, int n_cu) {
+  PairPlan p{};
+  int r_cap = (int)std::min<long long>(RESIDENT_LDS_CAP / ((long long)K * 4 + 12), 16 * L3_MAX_RB);
+  r_cap -= r_cap % 16;
+  if (r_cap < 16 || k_ring(K) == 0) return p;
+  const int Ns[2] = {N_a, N_b};
+  for (int i = 0; i < 2; ++i) {
+    const PassPlan pp = plan_passes(Ns[i], r_cap, 4);
+    if (((K >> 3) * 2 + (L3_THREADS / pp.rows) - 1) / (L3_THREADS / pp.rows) > L3_WPT) return p;   // the slab is requested all at once
+    p.RB[i] = pp.RB;
+    p.passes[i] = (unsigned)pp.passes;
+    p.rows_per_pass[i] = pp.rows;
+    p.lds = std::max(p.lds, (size_t)K * (16 * pp.RB) * 4 + 12 * (size_t)pp.rows + 256 + 16);
+  }
+  const long long WT = (M + L3_TILE_M - 1) / L3_TILE_M;
+  p.ring = k_ring(K);
+  // row ranges: one workgroup per CU, every wave with at least two row tiles -- and NOT rounded down to a multiple of 8 as
+  // plan_row_ranges does: the kernel's XCD remap keeps a row range's passes together for any extent, and the launch is bound by the
+  // work of its slowest workgroup (an A pass: 128 features), not by the memory system, so the 15 more CUs of 51 x 5 workgroups against
+  // 48 x 5 on 256 CUs are worth more than the few row ranges that straddle two XCDs cost
+  const long long passes = (long long)p.passes[0] + p.passes[1];
+  p.gx = (unsigned)std::max<long long>(1, std::min<long long>(n_cu / passes, WT / (2 * (L3_THREADS / 64))));
+  p.covered = true;
+  return p;
+}
+
 // ---- the streamed kernel (gemm_f16x3_stream.hip).  XMODE 0: a Linear; 1 / 2: a convolution on an NCHW / channels-last
 // operand, M = T H W pixels, N = Cout, K = taps * Cin
 inline bool stream_linear_covered(long long M, int N, int K) {

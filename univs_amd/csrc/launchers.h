@@ -54,6 +54,11 @@ int linear_split_f32(const float* x, const float* w, const float* bias, const fl
 int linear_f16x3_f32(const float* x, const float* w, const float* bias, const float* residual, float* y, long long M, int N,
                      int K, int epi, hipStream_t st, int blk_rows, int blk_cols, const float* winv, int n_cu);
 
+// ---- linear_pair_f16x3.hip: returns 1 if launched, 0 if not covered, < 0 on error
+int linear_pair_f16x3_f32(const float* x, const float* add, long long add_rows, const void* wp_a, const float* winv_a, const float* bias_a,
+                          int N_a, int blk_cols_a, float* y_a, const void* wp_b, const float* winv_b, const float* bias_b, int N_b,
+                          int blk_cols_b, float* y_b, long long M, int K, long long blk_rows, hipStream_t st);
+
 // ---- gemm_f16x3_stream.hip: returns UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the shape or alignment is not covered, or the launch's error
 int conv3x3_nhwc_f16x3_f32(const float* x, const void* wp, const float* winv, float* y, int T, int Cin, int Cout, int H, int W,
                            hipStream_t st);

@@ -23,7 +23,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ... import fused_ops, ops
+from ... import encoder_ops, fused_ops, ops
 from ...layers import Conv2d, get_activation_fn, get_norm, layer_norm, linear, linear_act
 from ...registry import SEM_SEG_HEADS_REGISTRY, ShapeSpec, configurable
 from ..position_encoding import PositionEmbeddingSine
@@ -86,25 +86,54 @@ class MSDeformAttn(nn.Module):
             self._qproj_hm_cache = c
         return c[1], c[2]
 
+    def pair_applies(self, src, pos, ref_per_query, padding_mask=None):
+        """True where `forward(None, ..., query_pos=pos)` projects `src` and `src + pos` in one launch (SWITCHES.encoder_pair;
+        encoder_ops.linear_pair_blocked): where the generation-6 head-major path applies today -- its two `ops.linear_blocked` cover the
+        rows -- and `pos` is one frame's table.  The caller then has no use for `src + pos` as a tensor.  (`src`: any tensor of the
+        input's device and dtype with the frames in front, the NCHW maps included.)"""
+        return (SWITCHES.encoder_pair and SWITCHES.msda_strips and SWITCHES.msda_heads and ref_per_query is not None and pos is not None
+                and pos.dim() == 3 and int(src.shape[0]) * int(pos.shape[1]) >= encoder_ops.HEAD_MAJOR_MIN_ROWS
+                and src.is_cuda and src.dtype == torch.float32 and pos.dtype == torch.float32 and pos.dim() == 3 and pos.shape[0] == 1
+                and self.n_points == 4 and self.n_levels <= 4 and padding_mask is None and self.d_model == 32 * self.n_heads == 256
+                and ops._resident_presplit(self.value_proj.weight, 256)
+                and not ops.needs_grad(src, pos, self.value_proj.weight, self.sampling_offsets.weight, self.attention_weights.weight))
+
     def forward(self, query, reference_points, input_flatten, input_spatial_shapes,
-                input_level_start_index, input_padding_mask=None, ref_per_query=None, residual=None):
+                input_level_start_index, input_padding_mask=None, ref_per_query=None, residual=None, query_pos=None):
         """query [N,Lq,C]; reference_points [N|1,Lq,L,2]; input_flatten [N,S,C];
         input_spatial_shapes / input_level_start_index: python lists (or tensors).
+        `query` None with `query_pos` [1, Lq, C]: the query is `input_flatten + query_pos` (self-attention of the encoder), formed
+        inside the projection where `pair_applies`, as a tensor otherwise.
         `ref_per_query` [N|1, Lq, 2] (optional): the caller's promise that every level shares one reference point per query
         (the encoder's pixel centres, msdeformattn.py:143-158 with valid_ratio == 1) -- enables the head-major kernel.
         `residual` [N, Lq, C] (optional): added to the result in `output_proj`'s epilogue (the layer's `src + self_attn(...)`)."""
-        N, Len_q, _ = query.shape
+        pair = query is None and self.pair_applies(input_flatten, query_pos, ref_per_query, input_padding_mask)
+        if query is None and not pair:
+            query = input_flatten + query_pos
+        N, Len_q, _ = input_flatten.shape if query is None else query.shape
         _, Len_in, _ = input_flatten.shape
         M, L, P = self.n_heads, self.n_levels, self.n_points
-        if (SWITCHES.msda_strips and ref_per_query is not None and query.is_cuda and P == 4 and L <= 4 and Len_q == Len_in
-                and input_padding_mask is None and self.d_model == 32 * M and query.dtype == torch.float32):
+        like = input_flatten if query is None else query
+        if (SWITCHES.msda_strips and ref_per_query is not None and like.is_cuda and P == 4 and L <= 4 and Len_q == Len_in
+                and input_padding_mask is None and self.d_model == 32 * M and like.dtype == torch.float32):
             shapes = _shape_list(input_spatial_shapes)
             order = tuple(ops.msda_level_order(shapes))
             w_hm, b_hm = self._head_major_query_proj(order)
-            qp_hm = ops.linear_blocked(query, w_hm, b_hm, Len_q, 3 * L * P)
+            qp_hm = value_hm = None
+            if pair:
+                # both projections from one read of the input, `input_flatten + query_pos` summed in registers (csrc/linear_pair_f16x3.hip)
+                both = encoder_ops.linear_pair_blocked(input_flatten, query_pos, self.value_proj.weight, self.value_proj.bias, 32,
+                                                       w_hm, b_hm, 3 * L * P)
+                if both is not None:
+                    value_hm, qp_hm = both
+                else:
+                    query = input_flatten + query_pos
+            if qp_hm is None:
+                qp_hm = ops.linear_blocked(query, w_hm, b_hm, Len_q, 3 * L * P)
             if qp_hm is not None and SWITCHES.msda_heads:
                 # generation 6 (csrc/msda_heads.hip): value in blocks of one head, a lane owns a sample of a full head
-                value_hm = ops.linear_blocked(input_flatten, self.value_proj.weight, self.value_proj.bias, Len_in, 32)
+                if value_hm is None:
+                    value_hm = ops.linear_blocked(input_flatten, self.value_proj.weight, self.value_proj.bias, Len_in, 32)
                 if value_hm is not None:
                     output = ops.msda_forward_heads(value_hm, qp_hm, ref_per_query, shapes, input_level_start_index, M, P)
                     if output is not None:
@@ -115,6 +144,8 @@ class MSDeformAttn(nn.Module):
                     output = ops.msda_forward_strips(value_hm, qp_hm, ref_per_query, shapes, input_level_start_index, M, P)
                     if output is not None:
                         return self._project(output, residual)
+        if query is None:
+            query = input_flatten + query_pos
         value = linear(input_flatten, self.value_proj.weight, self.value_proj.bias)
         if input_padding_mask is not None:
             value = value.masked_fill(input_padding_mask[..., None], float(0))
@@ -168,17 +199,24 @@ class MSDeformAttnTransformerEncoderLayer(nn.Module):
         """`query` = `src + pos` when the caller already has it (the previous layer's norm2 pass made it);
         `want_next_query`: also return `out + pos` for the next layer (same pass as norm2); `ref_per_query`: see
         MSDeformAttn.forward."""
-        if query is None:
-            query = src if pos is None else src + pos
+        # the attention forms `src + pos` inside its projections: no query tensor here, none asked of the FFN kernel for the next layer
+        pair = self.self_attn.pair_applies(src, pos, ref_per_query, padding_mask)
+        query_pos = None
+        if pair:
+            query, query_pos, want_pos = None, pos, False
+        else:
+            want_pos = want_next_query and pos is not None
+            if query is None:
+                query = src if pos is None else src + pos
         fused = SWITCHES.fused_mlp and SWITCHES.split_linear and src.is_cuda and self.activation is F.relu
         if fused and SWITCHES.fused_norm1 and not torch.is_grad_enabled() and src.dtype == torch.float32:
             # `src + self_attn(...)` from output_proj's epilogue, then norm1 + linear1 + ReLU + linear2 + residual + norm2 (+ the next
             # layer's `src + pos`) in ONE kernel: norm1 is evaluated on the x tile in registers and is also the FFN's residual
             # (csrc/mlp_f16x3.hip: res_normed)
             sum1 = self.self_attn(query, reference_points, src, spatial_shapes, level_start_index, padding_mask,
-                                  ref_per_query=ref_per_query, residual=src)
+                                  ref_per_query=ref_per_query, residual=src, query_pos=query_pos)
             n1, n2 = (self.norm1.weight, self.norm1.bias, self.norm1.eps), (self.norm2.weight, self.norm2.bias, self.norm2.eps)
-            with_next = want_next_query and pos is not None
+            with_next = want_pos
             res = ops.mlp_fused(sum1, self.linear1.weight, self.linear1.bias, self.linear2.weight, self.linear2.bias, "relu",
                                 ln=n1, residual_normed=True, post_ln=n2, post_add=pos if with_next else None)
             if res is not None:
@@ -188,14 +226,14 @@ class MSDeformAttnTransformerEncoderLayer(nn.Module):
             src = layer_norm(self.norm1, sum1)
         else:
             src2 = self.self_attn(query, reference_points, src, spatial_shapes, level_start_index, padding_mask,
-                                  ref_per_query=ref_per_query)
+                                  ref_per_query=ref_per_query, query_pos=query_pos)
             src = layer_norm(self.norm1, src2, residual=src)
         ffn = None
         if fused:
             # linear1 + ReLU + linear2 + residual + norm2 (+ the next layer's `src + pos`) in ONE kernel: the [tokens, d_ffn]
             # activations stay in registers and the finished row is normalised before it is stored (csrc/mlp_f16x3.hip)
             n2 = (self.norm2.weight, self.norm2.bias, self.norm2.eps)
-            with_next = want_next_query and pos is not None
+            with_next = want_pos
             res = ops.mlp_fused(src, self.linear1.weight, self.linear1.bias, self.linear2.weight, self.linear2.bias, "relu",
                                 residual=src, post_ln=n2, post_add=pos if with_next else None)
             if res is not None:
@@ -204,7 +242,7 @@ class MSDeformAttnTransformerEncoderLayer(nn.Module):
                 return (res, None) if want_next_query else res
         if ffn is None:
             ffn = linear(linear_act(src, self.linear1, self.activation), self.linear2.weight, self.linear2.bias)
-        if want_next_query and pos is not None and src.is_cuda:
+        if want_pos and src.is_cuda:
             return layer_norm(self.norm2, ffn, residual=src, post_add=pos)
         src = layer_norm(self.norm2, ffn, residual=src)
         return (src, None) if want_next_query else src
@@ -277,11 +315,13 @@ class MSDeformAttnTransformerEncoderOnly(nn.Module):
                 self.__dict__["_lvl_pos_cache"] = (pkey, lvl_pos, list(pos_embeds))     # (the embeddings are kept alive with their addresses)
         query0 = None
         fast = None
+        # (where the first layer forms `src + pos` inside its projections, the second output is not asked for)
+        pair0 = srcs[0].is_cuda and lvl_pos.shape[0] == 1 and self.encoder.layers[0].self_attn.pair_applies(srcs[0], lvl_pos, True)
         if srcs[0].is_cuda and not torch.is_grad_enabled() and lvl_pos.shape[0] == 1:
             # NCHW -> tokens per level by the LDS tile transpose, written straight into the concatenated tensor, GroupNorm applied on
             # the way in, `src + pos` for the first layer as a second output: one launch per level (a concatenation of transposed views
             # runs at 0.6 TB/s: 175 us for the 99 MB of a 720p clip)
-            fast = ops.tokens_from_nchw(srcs, affines if affines is not None else [None] * len(srcs), lvl_pos.contiguous())
+            fast = ops.tokens_from_nchw(srcs, affines if affines is not None else [None] * len(srcs), None if pair0 else lvl_pos.contiguous())
         if fast is not None:
             src_flatten, query0 = fast
         else:

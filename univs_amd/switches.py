@@ -89,6 +89,10 @@ class Switches:
     # Swin stage outputs handed on as channels-last VIEWS of the token tensors (same shape and values as the NCHW copy); the pixel
     # decoder's 1 x 1 convolutions read them in place (fused_ops.conv1x1_fused); False: an LDS tile transpose per stage
     swin_channels_last: bool = True
+    # encoder layer: value_proj on `src` and the merged sampling-offset / attention-weight projection on `src + pos` in ONE launch that
+    # forms the sum in registers (encoder_ops.linear_pair_blocked, csrc/linear_pair_f16x3.hip); the previous layer's FFN kernel then
+    # writes no `src + pos`.  False: two launches on two tensors.  Bit-identical either way
+    encoder_pair: bool = True
 
 
 SWITCHES = Switches(
@@ -100,7 +104,8 @@ SWITCHES = Switches(
     fused_cross_attention=_flag("UNIVS_FUSED_XATTN", True), fused_norm1=_flag("UNIVS_FUSED_NORM1", True), small_linear=_flag("UNIVS_SMALL_LINEAR", True),
     resident_presplit=_flag("UNIVS_RESIDENT_PRESPLIT", True), small_mlp_chain=_flag("UNIVS_SMALL_MLP_CHAIN", True), fused_proca=_flag("UNIVS_FUSED_PROCA", True),
     fused_sampler=_flag("UNIVS_FUSED_SAMPLER", True), small_mlp_norm=_flag("UNIVS_SMALL_MLP_NORM", True),
-    fold_fpn_norm=_flag("UNIVS_FOLD_FPN_NORM", True), fold_attn_merge=_flag("UNIVS_FOLD_ATTN_MERGE", False), swin_channels_last=_flag("UNIVS_SWIN_CHANNELS_LAST", True))
+    fold_fpn_norm=_flag("UNIVS_FOLD_FPN_NORM", True), fold_attn_merge=_flag("UNIVS_FOLD_ATTN_MERGE", False), swin_channels_last=_flag("UNIVS_SWIN_CHANNELS_LAST", True),
+    encoder_pair=_flag("UNIVS_ENCODER_PAIR", True))
 if SWITCHES.sampler not in ("auto", "reference", "device"):
     raise ValueError(f"UNIVS_SAMPLER={SWITCHES.sampler!r} (expected 'auto', 'reference' or 'device')")
 
