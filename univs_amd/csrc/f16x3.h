@@ -1,5 +1,6 @@
-// Shared by the three-product fp16 GEMM kernels (linear_f16x3.hip: W resident in LDS; gemm_f16x3_stream.hip: W pre-split in
-// global memory and streamed through LDS -- wide-K Linears and the 3 x 3 convolution).
+// The fp16 two-part split, row scales, GELU and instrumentation macros of the three-product kernels: included by f16x3_kstep.h (the k-step
+// of linear_f16x3.hip, linear_pair_f16x3.hip, gemm_f16x3_stream.hip), gemm_f16x3_tile.hip, mlp_f16x3.hip, small_linear.hip
+// and the attention cores (cross_attn.hip, window_attn_f16.hip).
 #pragma once
 #include "common.h"
 

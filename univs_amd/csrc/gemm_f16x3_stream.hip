@@ -13,7 +13,7 @@
 // Features per pass (128, or 64 for short tall-K problems), passes, row ranges and LDS bytes: plan_stream (gemm_plan.h).
 #include "common.h"
 #include "config.h"
-#include "f16x3.h"
+#include "f16x3_kstep.h"
 #include "gemm_plan.h"
 #include "launchers.h"
 
@@ -236,36 +236,11 @@ __global__ __launch_bounds__(GS_THREADS, 512 / GS_THREADS) void gemm_f16x3_strea
   f32x4 acc[RB][2];
   int eset[2];
   float sx[2], sx_inv[2];
-  constexpr int NB = RB > 6 ? 4 : 2;
-  constexpr int BSZ = (RB + NB - 1) / NB;
-  u32x4 afr[2][BSZ][2];
-  const unsigned a_lane = (unsigned)((g * 2 * Rp + j) * 16);
-  const unsigned a_kstep = (unsigned)(8 * Rp * 16);
-  const unsigned a_part = (unsigned)(Rp * 16);
-  // (the block and part offsets of a read are immediates of the instruction: linear_f16x3.hip)
-  auto read_batch = [&](u32x4 (&d)[BSZ][2], unsigned base, auto bc) __attribute__((always_inline)) {
-    constexpr int b = decltype(bc)::value;
-    l3_static_for<0, BSZ>([&](auto qc) __attribute__((always_inline)) {
-      constexpr int q = decltype(qc)::value;
-      constexpr int rb = b * BSZ + q < RB ? b * BSZ + q : RB - 1;
-      u32x4& dh = d[q][0];
-      u32x4& dm = d[q][1];
-      const unsigned aa = base;
-      asm volatile("ds_read_b128 %0, %2 offset:%3\n\tds_read_b128 %1, %2 offset:%4"
-                   : "=&v"(dh), "=&v"(dm)
-                   : "v"(aa), "n"(rb * 256), "n"(rb * 256 + Rp * 16)
-                   : "memory");
-    });
-  };
-  auto wait_batch = [&](u32x4 (&d)[BSZ][2]) __attribute__((always_inline)) {
-    if constexpr (BSZ == 1)
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(d[0][0]), "+v"(d[0][1]) : : "memory");
-    else if constexpr (BSZ == 2)
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(d[0][0]), "+v"(d[0][1]), "+v"(d[1][0]), "+v"(d[1][1]) : : "memory");
-    else
-      asm volatile("s_waitcnt lgkmcnt(0)"
-                   : "+v"(d[0][0]), "+v"(d[0][1]), "+v"(d[1][0]), "+v"(d[1][1]), "+v"(d[2][0]), "+v"(d[2][1]) : : "memory");
-  };
+  using KS_ = KStep<RB>;                                         // the A-fragment pipeline of f16x3_kstep.h
+  constexpr int NB = KS_::NB;
+  typename KS_::Batch afr[2];
+  const unsigned a_lane = KS_::lane(g, j);
+  auto read_batch = l3_batch_reader<RB>();
 
   TileRows t_cur, t_next;
   tile_rows(wg0 + wave, t_cur);
@@ -300,8 +275,7 @@ __global__ __launch_bounds__(GS_THREADS, 512 / GS_THREADS) void gemm_f16x3_strea
     }
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) acc[rb][0] = acc[rb][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    eset[0] = eset[1] = -1000;
-    sx[0] = sx[1] = sx_inv[0] = sx_inv[1] = 1.0f;
+    l3_row_scale_reset(eset, sx, sx_inv);
 #pragma unroll 1
     for (int q = 0; q < KG; ++q, ++gq) {
       __syncthreads();                                           // slab gq is complete; the other buffer is free
@@ -329,16 +303,10 @@ __global__ __launch_bounds__(GS_THREADS, 512 / GS_THREADS) void gemm_f16x3_strea
             __builtin_amdgcn_sched_barrier(0);                   // one column tile's pairs at a time: registers
           }
         }
-        // ---- the running row scale (linear_f16x3.hip)
-        bool need = false;
+        // ---- the running row scale (f16x3_kstep.h).  The lowering is l3_row_scale_lower's text in place: with the call, the kernels of eight
+        // feature blocks -- at the 256-register limit -- spill other registers than tests/test_seam_fold_cpu.py pins
         int enew[2];
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          const unsigned mk = l3_row_max(l3_absmax8(raw[u][c][0], raw[u][c][1]));
-          enew[c] = max(-100, min((int)((mk >> 23) & 255u) - 127, 128));
-          need = need || (enew[c] > eset[c] + 2);
-        }
-        if (__builtin_amdgcn_ballot_w64(need) != 0) {
+        if (__builtin_amdgcn_ballot_w64(l3_row_scale_need(raw[u], eset, enew)) != 0) {
 #pragma unroll
           for (int c = 0; c < 2; ++c) {
             const bool mine = enew[c] > eset[c] + 2;
@@ -363,24 +331,11 @@ __global__ __launch_bounds__(GS_THREADS, 512 / GS_THREADS) void gemm_f16x3_strea
         __builtin_amdgcn_sched_barrier(0);
         l3_static_for<0, NB>([&](auto bc) __attribute__((always_inline)) {
           constexpr int b = decltype(bc)::value;
-          wait_batch(afr[b & 1]);
-          if constexpr (b + 1 < NB) read_batch(afr[(b + 1) & 1], a_buf + (unsigned)u * a_kstep, std::integral_constant<int, b + 1>{});
-          else if (u + 1 < RING) read_batch(afr[0], a_buf + (unsigned)(u + 1) * a_kstep, std::integral_constant<int, 0>{});
+          l3_wait_batch(afr[b & 1]);
+          if constexpr (b + 1 < NB) read_batch(afr[(b + 1) & 1], a_buf + (unsigned)u * KS_::kstep, std::integral_constant<int, b + 1>{});
+          else if (u + 1 < RING) read_batch(afr[0], a_buf + (unsigned)(u + 1) * KS_::kstep, std::integral_constant<int, 0>{});
           __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int qq = 0; qq < BSZ; ++qq) {
-            const int rb = b * BSZ + qq;
-            if (rb < RB) {
-              const f16x8 ah = __builtin_bit_cast(f16x8, afr[b & 1][qq][0]);
-              const f16x8 am = __builtin_bit_cast(f16x8, afr[b & 1][qq][1]);
-              acc[rb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am, bh[0], acc[rb][0], 0, 0, 0);
-              acc[rb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am, bh[1], acc[rb][1], 0, 0, 0);
-              acc[rb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bm[0], acc[rb][0], 0, 0, 0);
-              acc[rb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bm[1], acc[rb][1], 0, 0, 0);
-              acc[rb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[0], acc[rb][0], 0, 0, 0);
-              acc[rb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[1], acc[rb][1], 0, 0, 0);
-            }
-          }
+          l3_mfma_batch<RB, b>(afr[b & 1], bh, bm, acc);
           __builtin_amdgcn_sched_barrier(0);
         });
       }

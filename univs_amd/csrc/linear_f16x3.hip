@@ -25,7 +25,7 @@
 // What is launched -- coverage, passes, row ranges, LDS bytes -- is plan_f16x3_resident (gemm_plan.h), shared with linear_split.hip.
 #include "common.h"
 #include "config.h"
-#include "f16x3.h"
+#include "f16x3_kstep.h"
 #include "gemm_plan.h"
 #include "launchers.h"
 
@@ -180,11 +180,7 @@ __global__ __launch_bounds__(L3_THREADS, 1) void linear_f16x3(const float* __res
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(epi == L3_EPI_RESIDUAL ? Res : X), 0, (int)((long long)M * N * 4), 0x00020000);
 
   f32x4 acc[RB][2];
-  // Row scales of x WITHOUT a pass of their own: a running scale per row.  Before a k-step is split its row maximum (over
-  // the four lanes that hold the row's k-groups) is compared with the exponent the current scale was set for; a row whose
-  // new maximum would leave fp16's range gets a smaller power of two, and the accumulators of that row -- sums of
-  // products under the old scale -- are multiplied by the ratio (exact).  The scale is set for 2^12 (three binades of room
-  // for later k-steps), only ever shrinks, and typically changes once or twice per row.
+  // the running scale of my two rows (f16x3_kstep.h)
   int eset[2];                                                    // exponent the scale of my two rows was set for
   float sx[2], sx_inv[2];
 
@@ -241,44 +237,12 @@ __global__ __launch_bounds__(L3_THREADS, 1) void linear_f16x3(const float* __res
     }
   };
 
-  // A fragments (W parts) come from LDS in NB batches of BSZ feature blocks, software-pipelined by hand: the reads of batch
-  // b + 1 are issued BEFORE the 6 BSZ MFMAs of batch b and waited for after them.  Left to the compiler, every ds_read_b128
-  // sat directly in front of its first use behind an `s_waitcnt lgkmcnt(0)` (ISA of the first version): ~100 clocks of
-  // exposed LDS latency per 3 MFMAs, and halving the MFMA work against the six-product kernel changed nothing.
-  constexpr int NB = RB > 6 ? 4 : 2;                             // even: the two buffers alternate across k-steps too
-  constexpr int BSZ = (RB + NB - 1) / NB;                        // 1 .. 3 blocks
-  u32x4 afr[2][BSZ][2];                                          // [buffer][block of the batch][part h, m]
-  // byte address of (k-step ks, my k-group g, part h, row j); blocks are 256 B apart, the m part Rp * 16 B further
-  const unsigned a_lane = (unsigned)((g * 2 * Rp + j) * 16);
-  const unsigned a_kstep = (unsigned)(8 * Rp * 16);
-  const unsigned a_part = (unsigned)(Rp * 16);
-  // the block (256 B) and part offsets of a read are IMMEDIATES of the instruction (batch index = a compile-time constant): one address
-  // register per k-step instead of two vector adds per read (16 of ~100 vector instructions per k-step at 128 features)
-  auto read_batch = [&](u32x4 (&d)[BSZ][2], int ks, auto bc) __attribute__((always_inline)) {
-    constexpr int b = decltype(bc)::value;
-    const unsigned a0 = a_lane + (unsigned)ks * a_kstep;
-    l3_static_for<0, BSZ>([&](auto qc) __attribute__((always_inline)) {
-      constexpr int q = decltype(qc)::value;
-      constexpr int rb = b * BSZ + q < RB ? b * BSZ + q : RB - 1;   // a short last batch re-reads the last block
-      u32x4& dh = d[q][0];                                       // (operands of an asm statement do not capture: name them first)
-      u32x4& dm = d[q][1];
-      const unsigned aa = a0;
-      asm volatile("ds_read_b128 %0, %2 offset:%3\n\tds_read_b128 %1, %2 offset:%4"
-                   : "=&v"(dh), "=&v"(dm)
-                   : "v"(aa), "n"(rb * 256), "n"(rb * 256 + Rp * 16)
-                   : "memory");
-    });
-  };
-  // all LDS traffic in flight is the batch about to be used; the operands tie the MFMAs below to this wait
-  auto wait_batch = [&](u32x4 (&d)[BSZ][2]) __attribute__((always_inline)) {
-    if constexpr (BSZ == 1)
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(d[0][0]), "+v"(d[0][1]) : : "memory");
-    else if constexpr (BSZ == 2)
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(d[0][0]), "+v"(d[0][1]), "+v"(d[1][0]), "+v"(d[1][1]) : : "memory");
-    else
-      asm volatile("s_waitcnt lgkmcnt(0)"
-                   : "+v"(d[0][0]), "+v"(d[0][1]), "+v"(d[1][0]), "+v"(d[1][1]), "+v"(d[2][0]), "+v"(d[2][1]) : : "memory");
-  };
+  // A fragments (W parts) from LDS, one batch ahead of the MFMAs that use them (f16x3_kstep.h)
+  using KS_ = KStep<RB>;
+  constexpr int NB = KS_::NB;
+  typename KS_::Batch afr[2];                                    // [buffer]: the batch in use and the one being read
+  const unsigned a_lane = KS_::lane(g, j);
+  auto read_batch = l3_batch_reader<RB>();
   auto group = [&](int ks0, bool last_group) __attribute__((always_inline)) {
     unsigned vo_ref[2];                                           // rows of the k-steps requested in this group
 #pragma unroll
@@ -286,28 +250,8 @@ __global__ __launch_bounds__(L3_THREADS, 1) void linear_f16x3(const float* __res
 #pragma unroll
     for (int u = 0; u < RING; ++u) {
       const int ks = ks0 + u;
-      // ---- the running row scale
-      bool need = false;
-      int enew[2];
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const unsigned mk = l3_row_max(l3_absmax8(raw[u][c][0], raw[u][c][1]));
-        enew[c] = max(-100, min((int)((mk >> 23) & 255u) - 127, 128));      // 2^e <= max < 2^(e+1)
-        need = need || (enew[c] > eset[c] + 2);
-      }
-      if (__builtin_amdgcn_ballot_w64(need) != 0 && ablate != 1) {           // rare
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          const bool mine = enew[c] > eset[c] + 2;
-          const int en = mine ? enew[c] : eset[c];
-          const float ratio = __builtin_bit_cast(float, (unsigned)(127 + max(eset[c] - en, -126)) << 23);   // 2^(old - new) <= 1
-#pragma unroll
-          for (int rb = 0; rb < RB; ++rb) acc[rb][c] *= ratio;
-          eset[c] = en;
-          sx[c] = __builtin_bit_cast(float, (unsigned)(127 + 12 - en) << 23);
-          sx_inv[c] = __builtin_bit_cast(float, (unsigned)(127 - 12 + en) << 23);
-        }
-      }
+      int enew[2];                                                // the running row scale
+      if (__builtin_amdgcn_ballot_w64(l3_row_scale_need(raw[u], eset, enew)) != 0 && ablate != 1) l3_row_scale_lower(enew, acc, eset, sx, sx_inv);   // rare
       float s0 = sx[0], s1 = sx[1];
       asm volatile("" : "+v"(s0), "+v"(s1) : : "memory");      // pins the consumption of ring stage u here
       f16x8 bh[2], bm[2];
@@ -322,38 +266,23 @@ __global__ __launch_bounds__(L3_THREADS, 1) void linear_f16x3(const float* __res
       const int ks_next = (ks + 1 == KS) ? 0 : ks + 1;           // the next k-step's first batch (W is the same for every tile)
       l3_static_for<0, NB>([&](auto bc) __attribute__((always_inline)) {
         constexpr int b = decltype(bc)::value;
-        wait_batch(afr[b & 1]);
-        if constexpr (b + 1 < NB) read_batch(afr[(b + 1) & 1], ks, std::integral_constant<int, b + 1>{});
-        else read_batch(afr[0], ks_next, std::integral_constant<int, 0>{});
+        l3_wait_batch(afr[b & 1]);
+        if constexpr (b + 1 < NB) read_batch(afr[(b + 1) & 1], a_lane + (unsigned)ks * KS_::kstep, std::integral_constant<int, b + 1>{});
+        else read_batch(afr[0], a_lane + (unsigned)ks_next * KS_::kstep, std::integral_constant<int, 0>{});
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int q = 0; q < BSZ; ++q) {
-          const int rb = b * BSZ + q;
-          if (rb < RB) {
-            const f16x8 ah = __builtin_bit_cast(f16x8, afr[b & 1][q][0]);
-            const f16x8 am = __builtin_bit_cast(f16x8, afr[b & 1][q][1]);
-            // smallest terms first: m*h', h*m', h*h'
-            acc[rb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am, bh[0], acc[rb][0], 0, 0, 0);
-            acc[rb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am, bh[1], acc[rb][1], 0, 0, 0);
-            acc[rb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bm[0], acc[rb][0], 0, 0, 0);
-            acc[rb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bm[1], acc[rb][1], 0, 0, 0);
-            acc[rb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[0], acc[rb][0], 0, 0, 0);
-            acc[rb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[1], acc[rb][1], 0, 0, 0);
-          }
-        }
+        l3_mfma_batch<RB, b>(afr[b & 1], bh, bm, acc);
         __builtin_amdgcn_sched_barrier(0);
       });
     }
   };
 
-  read_batch(afr[0], 0, std::integral_constant<int, 0>{});       // batch 0 of the first k-step
+  read_batch(afr[0], a_lane, std::integral_constant<int, 0>{});                          // batch 0 of the first k-step
 
 #pragma unroll 1
   for (int tile = 0; tile < ntiles; ++tile) {
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) acc[rb][0] = acc[rb][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    eset[0] = eset[1] = ablate == 1 ? 12 : -1000;                // the first k-step sets the scale
-    sx[0] = sx[1] = sx_inv[0] = sx_inv[1] = 1.0f;
+    l3_row_scale_reset(eset, sx, sx_inv, ablate == 1);
 #pragma unroll 1
     for (int ks0 = 0; ks0 < KS; ks0 += RING) group(ks0, ks0 + RING >= KS);
     UNIVS_GT(g_l3_trace, gts, 3 + 2 * tile);

@@ -17,14 +17,16 @@
 // flight as an A pass's RING stages of x (a k-step of B moves twice the bytes).  With x at the full depth and `add` at half of it, or
 // at a quarter, the 96-feature body spills 53 / 16 registers.  The kernel is the two pass bodies behind one uniform branch;
 // profiles/encoder_pair_resources_v1.txt has the build's register and scratch figures (no scratch, no spills).
-// The k-loop is a copy of linear_f16x3's, not a shared function: that kernel's code stays byte for byte what its tests pin.
+// The k-step -- fragment pipeline, running row scale, three products -- is f16x3_kstep.h, shared with linear_f16x3; the pass around it
+// (tile ownership, slab, rings, epilogue) is a second text of that kernel's: as one function both kernels compile into other, longer
+// code ("One k-step core").
 // What is launched is plan_f16x3_pair (gemm_plan.h).
 // MEASURED (profiles/encoder_pair_clip_breakdown_{parent,this}.txt, 96 600 rows): 148 us against the 62 + 88 us of the two launches --
 // parity: these projections are bound by the work of their workgroups, all CUs busy either way.  What the launch buys is upstream: the
 // FFN kernel without its 99 MB second output (330 -> 299 us per layer), no `src + pos` from tokens_from_nchw, one launch fewer per layer.
 #include "common.h"
 #include "config.h"
-#include "f16x3.h"
+#include "f16x3_kstep.h"
 #include "gemm_plan.h"
 #include "launchers.h"
 
@@ -154,36 +156,11 @@ __device__ __forceinline__ void pair_pass(const PairArgs& a, const PairProblem& 
     }
   };
 
-  // A fragments from LDS in NB batches of BSZ feature blocks, the reads of batch b + 1 issued before the MFMAs of batch b (linear_f16x3)
-  constexpr int NB = RB > 6 ? 4 : 2;
-  constexpr int BSZ = (RB + NB - 1) / NB;
-  u32x4 afr[2][BSZ][2];
-  const unsigned a_lane = (unsigned)((g * 2 * Rp + j) * 16);
-  const unsigned a_kstep = (unsigned)(8 * Rp * 16);
-  auto read_batch = [&](u32x4 (&d)[BSZ][2], int ks, auto bc) __attribute__((always_inline)) {
-    constexpr int b = decltype(bc)::value;
-    const unsigned a0 = a_lane + (unsigned)ks * a_kstep;
-    l3_static_for<0, BSZ>([&](auto qc) __attribute__((always_inline)) {
-      constexpr int q = decltype(qc)::value;
-      constexpr int rb = b * BSZ + q < RB ? b * BSZ + q : RB - 1;
-      u32x4& dh = d[q][0];
-      u32x4& dm = d[q][1];
-      const unsigned aa = a0;
-      asm volatile("ds_read_b128 %0, %2 offset:%3\n\tds_read_b128 %1, %2 offset:%4"
-                   : "=&v"(dh), "=&v"(dm)
-                   : "v"(aa), "n"(rb * 256), "n"(rb * 256 + Rp * 16)
-                   : "memory");
-    });
-  };
-  auto wait_batch = [&](u32x4 (&d)[BSZ][2]) __attribute__((always_inline)) {
-    if constexpr (BSZ == 1)
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(d[0][0]), "+v"(d[0][1]) : : "memory");
-    else if constexpr (BSZ == 2)
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(d[0][0]), "+v"(d[0][1]), "+v"(d[1][0]), "+v"(d[1][1]) : : "memory");
-    else
-      asm volatile("s_waitcnt lgkmcnt(0)"
-                   : "+v"(d[0][0]), "+v"(d[0][1]), "+v"(d[1][0]), "+v"(d[1][1]), "+v"(d[2][0]), "+v"(d[2][1]) : : "memory");
-  };
+  using KS_ = KStep<RB>;                                         // the A-fragment pipeline of f16x3_kstep.h
+  constexpr int NB = KS_::NB;
+  typename KS_::Batch afr[2];
+  const unsigned a_lane = KS_::lane(g, j);
+  auto read_batch = l3_batch_reader<RB>();
   auto group = [&](int ks0, bool last_group) __attribute__((always_inline)) {
 #pragma unroll
     for (int u = 0; u < RING; ++u) {
@@ -195,28 +172,8 @@ __device__ __forceinline__ void pair_pass(const PairArgs& a, const PairProblem& 
           raw[u][c][1] = raw[u][c][1] + addr[u % AR][c][1];
         }
       }
-      // ---- the running row scale
-      bool need = false;
-      int enew[2];
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const unsigned mk = l3_row_max(l3_absmax8(raw[u][c][0], raw[u][c][1]));
-        enew[c] = max(-100, min((int)((mk >> 23) & 255u) - 127, 128));      // 2^e <= max < 2^(e+1)
-        need = need || (enew[c] > eset[c] + 2);
-      }
-      if (__builtin_amdgcn_ballot_w64(need) != 0) {                          // rare
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          const bool mine = enew[c] > eset[c] + 2;
-          const int en = mine ? enew[c] : eset[c];
-          const float ratio = __builtin_bit_cast(float, (unsigned)(127 + max(eset[c] - en, -126)) << 23);   // 2^(old - new) <= 1
-#pragma unroll
-          for (int rb = 0; rb < RB; ++rb) acc[rb][c] *= ratio;
-          eset[c] = en;
-          sx[c] = __builtin_bit_cast(float, (unsigned)(127 + 12 - en) << 23);
-          sx_inv[c] = __builtin_bit_cast(float, (unsigned)(127 - 12 + en) << 23);
-        }
-      }
+      int enew[2];                                                // the running row scale (f16x3_kstep.h)
+      if (__builtin_amdgcn_ballot_w64(l3_row_scale_need(raw[u], eset, enew)) != 0) l3_row_scale_lower(enew, acc, eset, sx, sx_inv);   // rare
       float s0 = sx[0], s1 = sx[1];
       asm volatile("" : "+v"(s0), "+v"(s1) : : "memory");      // pins the consumption of ring stage u here
       f16x8 bh[2], bm[2];
@@ -238,38 +195,23 @@ __device__ __forceinline__ void pair_pass(const PairArgs& a, const PairProblem& 
       const int ks_next = (ks + 1 == KS) ? 0 : ks + 1;
       l3_static_for<0, NB>([&](auto bc) __attribute__((always_inline)) {
         constexpr int b = decltype(bc)::value;
-        wait_batch(afr[b & 1]);
-        if constexpr (b + 1 < NB) read_batch(afr[(b + 1) & 1], ks, std::integral_constant<int, b + 1>{});
-        else read_batch(afr[0], ks_next, std::integral_constant<int, 0>{});
+        l3_wait_batch(afr[b & 1]);
+        if constexpr (b + 1 < NB) read_batch(afr[(b + 1) & 1], a_lane + (unsigned)ks * KS_::kstep, std::integral_constant<int, b + 1>{});
+        else read_batch(afr[0], a_lane + (unsigned)ks_next * KS_::kstep, std::integral_constant<int, 0>{});
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int q = 0; q < BSZ; ++q) {
-          const int rb = b * BSZ + q;
-          if (rb < RB) {
-            const f16x8 ah = __builtin_bit_cast(f16x8, afr[b & 1][q][0]);
-            const f16x8 am = __builtin_bit_cast(f16x8, afr[b & 1][q][1]);
-            // smallest terms first: m*h', h*m', h*h'
-            acc[rb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am, bh[0], acc[rb][0], 0, 0, 0);
-            acc[rb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am, bh[1], acc[rb][1], 0, 0, 0);
-            acc[rb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bm[0], acc[rb][0], 0, 0, 0);
-            acc[rb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bm[1], acc[rb][1], 0, 0, 0);
-            acc[rb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[0], acc[rb][0], 0, 0, 0);
-            acc[rb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[1], acc[rb][1], 0, 0, 0);
-          }
-        }
+        l3_mfma_batch<RB, b>(afr[b & 1], bh, bm, acc);
         __builtin_amdgcn_sched_barrier(0);
       });
     }
   };
 
-  read_batch(afr[0], 0, std::integral_constant<int, 0>{});       // batch 0 of the first k-step
+  read_batch(afr[0], a_lane, std::integral_constant<int, 0>{});                          // batch 0 of the first k-step
 
 #pragma unroll 1
   for (int tile = 0; tile < ntiles; ++tile) {
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) acc[rb][0] = acc[rb][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    eset[0] = eset[1] = -1000;                                   // the first k-step sets the scale
-    sx[0] = sx[1] = sx_inv[0] = sx_inv[1] = 1.0f;
+    l3_row_scale_reset(eset, sx, sx_inv);
 #pragma unroll 1
     for (int ks0 = 0; ks0 < KS; ks0 += RING) group(ks0, ks0 + RING >= KS);
     epilogue(tile);
