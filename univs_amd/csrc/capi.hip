@@ -10,6 +10,7 @@
 #include "../../include/univs_fused_hip.h"
 #include "../../include/univs_pvos_hip.h"
 #include "../../include/univs_semantic_hip.h"
+#include "../../include/univs_swin_hip.h"
 #include "common.h"
 #include "config.h"
 #include "launchers.h"
@@ -957,6 +958,19 @@ int univs_window_attention_image_mma(const float* qkv, const float* qkv_bias, co
   if (rc == UNIVS_ERR_NOT_IMPLEMENTED && mma == UNIVS_MMA_F16X3)      // windows beyond 9 x 9: the exact kernel (same accuracy class)
     return univs_window_attention_image_f32(qkv, qkv_bias, bias, shift_mask, B, H, W, ws, shift, nH, hd, scale, out, stream);
   return rc;
+}
+
+int univs_swin_window_attention_qkv_presplit_f32(const float* x, const void* wp, const float* winv, const float* qkv_bias,
+                                                 const float* rel_bias, const float* shift_mask, int B, int H, int W, int ws, int shift,
+                                                 int nH, int C, float scale, float* out, void* stream) {
+  const Entry e("univs_swin_window_attention_qkv_presplit_f32", stream);
+  if (B < 0 || H < 1 || W < 1 || ws < 1 || shift < 0 || shift >= ws || nH < 1 || C < 1)
+    return e.invalid("bad dimensions B=%d H=%d W=%d ws=%d shift=%d nH=%d C=%d", B, H, W, ws, shift, nH, C);
+  if (B == 0) return UNIVS_OK;
+  if (!x || !wp || !winv || !rel_bias || !out) return e.null_pointer();
+  return e.launched(window_attention_qkv_f16x3(x, wp, winv, qkv_bias, rel_bias, shift ? shift_mask : nullptr, B, H, W, ws, shift, nH, C, scale,
+                                               out, e.st),
+                    "not covered (7 x 7 windows, C == 32 nH in {96, 192}, x and the weight image 16-byte aligned, B H W C 4 < 2^31 - 1)");
 }
 
 int univs_msda_prepare_f32(const float* proj, int row_stride, int n_off, const float* ref_points,

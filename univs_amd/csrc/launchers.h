@@ -113,6 +113,11 @@ int window_attention_image_f16mma(const float* qkv, const float* qkv_bias, const
                                   int H, int W, int ws, int shift, int nH, int hd, float scale, int terms, float* out,
                                   hipStream_t st);
 
+// ---- window_attn_qkv.hip: returns 1 if launched, 0 if not covered, < 0 on error
+int window_attention_qkv_f16x3(const float* x, const void* wp, const float* winv, const float* qkv_bias, const float* bias,
+                               const float* shift_mask, int B, int H, int W, int ws, int shift, int nH, int C, float scale, float* out,
+                               hipStream_t st);
+
 // ---- resample.hip: returns UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the shape or alignment is not covered, or the launch's error
 int bilinear_resample_f32(const float* in, const float* addend, float* out, long long planes, int Hin, int Win,
                           int Hout, int Wout, hipStream_t st);

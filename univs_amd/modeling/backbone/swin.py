@@ -18,7 +18,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ... import ops
+from ... import ops, swin_ops
 from ...layers import fp32_region, layer_norm
 from ...registry import BACKBONE_REGISTRY, ShapeSpec
 
@@ -129,15 +129,33 @@ class WindowAttention(nn.Module):
             self._bias_cache = (key, b.detach())
         return self._bias_cache[1]
 
+    def fused_qkv_applies(self, x):
+        """True where `forward_image` asks for the attention launch that computes q, k, v itself (SWITCHES.swin_fused_qkv): three-product
+        attention, no autograd, a whole contiguous qkv.weight, and -- so that the result keeps the bits of the two launches -- where
+        `_linear(self.qkv, x)` takes the three-product Linear today (`ops.linear_fused`: 2048 tokens and more)."""
+        w = self.qkv.weight
+        rows = x.numel() // max(int(x.shape[-1]), 1)
+        return (SWITCHES.swin_fused_qkv and self.mma == "f16x3" and x.is_cuda and x.dtype == torch.float32
+                and SWITCHES.swin_fused_linear and (SWITCHES.swin_fused_parts & 1) and self.dim <= SWITCHES.linear_kmax
+                and rows >= 2048 and rows * 3 * self.dim * 4 < 2 ** 31 - 1
+                and self.window_size[0] == self.window_size[1] == 7 and self.dim in (96, 192) and self.dim == 32 * self.num_heads
+                and w._base is None and w.is_contiguous() and not ops.needs_grad(x, w, self.qkv.bias, self.relative_position_bias_table))
+
     def forward_image(self, x, H, W, shift, mask=None, residual=None):
         """x: [B, H*W, C] tokens in image order.  Same result as pad -> roll -> window_partition -> forward ->
         window_reverse -> roll -> crop (the reference block, swin.py:252-284), with all of that data movement
         done by index arithmetic inside the attention kernel (the qkv / proj Linears are per token, so they
         commute with the partition).  `residual` [B, H*W, C]: added to the result."""
         B, L, C = x.shape
-        qkv = _linear(self.qkv, x).view(B, L, 3, self.num_heads, C // self.num_heads)
-        out = ops.window_attention_image(qkv, self.qkv.bias, self._bias(), mask, H, W, self.window_size[0], shift,
-                                         self.scale, mma=self.mma)
+        out = None
+        if self.fused_qkv_applies(x):
+            # q, k, v computed inside the attention launch (csrc/window_attn_qkv.hip): the qkv tensor is never written
+            out = swin_ops.window_attention_qkv(x, self.qkv.weight, self.qkv.bias, self._bias(), mask, H, W, self.window_size[0], shift,
+                                                self.scale)
+        if out is None:
+            qkv = _linear(self.qkv, x).view(B, L, 3, self.num_heads, C // self.num_heads)
+            out = ops.window_attention_image(qkv, self.qkv.bias, self._bias(), mask, H, W, self.window_size[0], shift,
+                                             self.scale, mma=self.mma)
         if residual is None:
             return _linear(self.proj, out)
         # the block's `shortcut + attn branch` (swin.py:286) in the proj Linear's epilogue

@@ -93,6 +93,10 @@ class Switches:
     # forms the sum in registers (encoder_ops.linear_pair_blocked, csrc/linear_pair_f16x3.hip); the previous layer's FFN kernel then
     # writes no `src + pos`.  False: two launches on two tensors.  Bit-identical either way
     encoder_pair: bool = True
+    # Swin stages 1-2 (7 x 7 windows, C in {96, 192}): the qkv Linear inside the window-attention launch (swin_ops.window_attention_qkv,
+    # csrc/window_attn_qkv.hip) -- no [B, H*W, 3C] tensor; taken where the Linear would run on the three-product kernels (2048 tokens
+    # and more).  False: the Linear and the attention as two launches.  Bit-identical either way
+    swin_fused_qkv: bool = True
 
 
 SWITCHES = Switches(
@@ -105,7 +109,7 @@ SWITCHES = Switches(
     resident_presplit=_flag("UNIVS_RESIDENT_PRESPLIT", True), small_mlp_chain=_flag("UNIVS_SMALL_MLP_CHAIN", True), fused_proca=_flag("UNIVS_FUSED_PROCA", True),
     fused_sampler=_flag("UNIVS_FUSED_SAMPLER", True), small_mlp_norm=_flag("UNIVS_SMALL_MLP_NORM", True),
     fold_fpn_norm=_flag("UNIVS_FOLD_FPN_NORM", True), fold_attn_merge=_flag("UNIVS_FOLD_ATTN_MERGE", False), swin_channels_last=_flag("UNIVS_SWIN_CHANNELS_LAST", True),
-    encoder_pair=_flag("UNIVS_ENCODER_PAIR", True))
+    encoder_pair=_flag("UNIVS_ENCODER_PAIR", True), swin_fused_qkv=_flag("UNIVS_SWIN_FUSED_QKV", True))
 if SWITCHES.sampler not in ("auto", "reference", "device"):
     raise ValueError(f"UNIVS_SAMPLER={SWITCHES.sampler!r} (expected 'auto', 'reference' or 'device')")
 
