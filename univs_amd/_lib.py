@@ -1,6 +1,6 @@
 """ctypes binding of libunivs_hip.so (the C ABI declared in include/univs_hip.h, include/univs_eval_hip.h,
-include/univs_fused_hip.h, include/univs_pvos_hip.h, include/univs_semantic_hip.h, include/univs_encoder_hip.h and
-include/univs_swin_hip.h).
+include/univs_fused_hip.h, include/univs_pvos_hip.h, include/univs_semantic_hip.h, include/univs_encoder_hip.h,
+include/univs_swin_hip.h and include/univs_frames_hip.h).
 
 The header is the one statement of the ABI: `SIGNATURES` (restype / argtypes of every `univs_*` symbol) and `CONFIG_FIELDS` (the
 members of `struct UnivsConfig`) are read from its text when this module loads -- no table is kept by hand.
@@ -99,6 +99,10 @@ with open(ENCODER_HEADER_PATH) as _f:
 SWIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "univs_swin_hip.h")
 with open(SWIN_HEADER_PATH) as _f:
     SWIN_SIGNATURES = parse_signatures(_f.read())
+# The eighth header (include/univs_frames_hip.h: the test-time resize of decoded frames), likewise.
+FRAMES_HEADER_PATH = os.path.join(_HERE, "..", "include", "univs_frames_hip.h")
+with open(FRAMES_HEADER_PATH) as _f:
+    FRAMES_SIGNATURES = parse_signatures(_f.read())
 
 _lib = None
 
@@ -119,7 +123,8 @@ def load():
             "Build it with `python -m univs_amd.build`.")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (*SIGNATURES.items(), *EVAL_SIGNATURES.items(), *FUSED_SIGNATURES.items(),
-                              *PVOS_SIGNATURES.items(), *SEMANTIC_SIGNATURES.items(), *ENCODER_SIGNATURES.items(), *SWIN_SIGNATURES.items()):
+                              *PVOS_SIGNATURES.items(), *SEMANTIC_SIGNATURES.items(), *ENCODER_SIGNATURES.items(), *SWIN_SIGNATURES.items(),
+                              *FRAMES_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing -> loud
         fn.restype = res
         fn.argtypes = args

@@ -7,6 +7,7 @@
 
 #include "../../include/univs_encoder_hip.h"
 #include "../../include/univs_eval_hip.h"
+#include "../../include/univs_frames_hip.h"
 #include "../../include/univs_fused_hip.h"
 #include "../../include/univs_pvos_hip.h"
 #include "../../include/univs_semantic_hip.h"
@@ -923,6 +924,24 @@ int univs_semantic_quality_counts_f32(const float* mask_embed, const float* feat
   return e.covered(semantic_quality_counts_f32(mask_embed, features, T, N, C, HW, t_step, t_hi, t_lo, counts, e.st),
                    "not covered (ceil(T / t_step) HW < 2^31, C HW 4 < 2^31, ceil(T / t_step) <= 65535, N <= 2097120, C <= 315, or up to "
                    "1239 where few rows make a smaller LDS tile)");
+}
+
+// (include/univs_frames_hip.h)
+int univs_resize_frames_u8(const uint8_t* src, int T, int Hi, int Wi, int Ho, int Wo, const int32_t* first_x, const int32_t* count_x,
+                           const int32_t* coef_x, int ksize_x, const int32_t* first_y, const int32_t* count_y, const int32_t* coef_y,
+                           int ksize_y, int swap_rb, uint8_t* out, void* stream) {
+  const Entry e("univs_resize_frames_u8", stream);
+  if (T < 1 || Hi < 1 || Wi < 1 || Ho < 1 || Wo < 1) return e.invalid("bad arguments T=%d Hi=%d Wi=%d Ho=%d Wo=%d", T, Hi, Wi, Ho, Wo);
+  // 2 ceil(max(n_in / n_out, 1)) + 1 in integers
+  const long long kx = 2 * (((long long)(Wi > Wo ? Wi : Wo) + Wo - 1) / Wo) + 1, ky = 2 * (((long long)(Hi > Ho ? Hi : Ho) + Ho - 1) / Ho) + 1;
+  if (ksize_x != kx || ksize_y != ky)
+    return e.invalid("ksize_x=%d ksize_y=%d, but %d -> %d columns have %lld slots and %d -> %d rows %lld", ksize_x, ksize_y, Wi, Wo, kx, Hi, Ho,
+                     ky);
+  if (!src || !out || (Wi != Wo && (!first_x || !count_x || !coef_x)) || (Hi != Ho && (!first_y || !count_y || !coef_y)))
+    return e.null_pointer();
+  return e.covered(resize_frames_u8(src, T, Hi, Wi, Ho, Wo, first_x, count_x, coef_x, ksize_x, first_y, count_y, coef_y, ksize_y, swap_rb, out,
+                                    e.st),
+                   "not covered (ksize_x <= 9 and ksize_y <= 9: a down-scale up to 4; T Hi Wi 3 < 2^31, T 3 Ho Wo < 2^31)");
 }
 
 // The two window-attention entries on image-layout operands share their checks

@@ -223,4 +223,9 @@ int pvos_counts(const unsigned char* gt, const unsigned char* pred, int T, int H
 int semantic_quality_counts_f32(const float* mask_embed, const float* features, int T, int N, int C, int HW, int t_step, float t_hi,
                                 float t_lo, int* counts, hipStream_t st);
 
+// ---- frame_resize.hip: returns UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the sizes are not covered, or the launch's error
+int resize_frames_u8(const unsigned char* src, int T, int Hi, int Wi, int Ho, int Wo, const int* first_x, const int* count_x,
+                     const int* coef_x, int ksize_x, const int* first_y, const int* count_y, const int* coef_y, int ksize_y, int swap_rb,
+                     unsigned char* out, hipStream_t st);
+
 }  // namespace univs
