@@ -9,6 +9,7 @@
 #include "../../include/univs_eval_hip.h"
 #include "../../include/univs_frames_hip.h"
 #include "../../include/univs_fused_hip.h"
+#include "../../include/univs_prompts_hip.h"
 #include "../../include/univs_pvos_hip.h"
 #include "../../include/univs_semantic_hip.h"
 #include "../../include/univs_swin_hip.h"
@@ -942,6 +943,18 @@ int univs_resize_frames_u8(const uint8_t* src, int T, int Hi, int Wi, int Ho, in
   return e.covered(resize_frames_u8(src, T, Hi, Wi, Ho, Wo, first_x, count_x, coef_x, ksize_x, first_y, count_y, coef_y, ksize_y, swap_rb, out,
                                     e.st),
                    "not covered (ksize_x <= 9 and ksize_y <= 9: a down-scale up to 4; T Hi Wi 3 < 2^31, T 3 Ho Wo < 2^31)");
+}
+
+// (include/univs_prompts_hip.h)
+int univs_resize_rle_masks_u8(const int32_t* bounds, const int32_t* starts, long long n_bounds, int N, int H, int W, const int32_t* ty,
+                              const int32_t* tx, int Ho, int Wo, uint8_t* masks, int32_t* boxes, void* stream) {
+  const Entry e("univs_resize_rle_masks_u8", stream);
+  if (N < 0 || n_bounds < 0 || H < 1 || W < 1 || Ho < 1 || Wo < 1)
+    return e.invalid("bad arguments n_bounds=%lld N=%d H=%d W=%d Ho=%d Wo=%d", n_bounds, N, H, W, Ho, Wo);
+  if (N == 0) return UNIVS_OK;
+  if (!bounds || !starts || !ty || !tx || !masks || !boxes) return e.null_pointer();
+  return e.covered(resize_rle_masks_u8(bounds, starts, n_bounds, N, H, W, ty, tx, Ho, Wo, masks, boxes, e.st),
+                   "not covered (H W < 2^31, n_bounds < 2^31, N Ho Wo < 2^31)");
 }
 
 // The two window-attention entries on image-layout operands share their checks

@@ -228,4 +228,8 @@ int resize_frames_u8(const unsigned char* src, int T, int Hi, int Wi, int Ho, in
                      const int* coef_x, int ksize_x, const int* first_y, const int* count_y, const int* coef_y, int ksize_y, int swap_rb,
                      unsigned char* out, hipStream_t st);
 
+// ---- mask_prompt_resize.hip: returns UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the sizes are not covered, or the launch's error
+int resize_rle_masks_u8(const int* bounds, const int* starts, long long n_bounds, int N, int H, int W, const int* ty, const int* tx, int Ho,
+                        int Wo, unsigned char* masks, int* boxes, hipStream_t st);
+
 }  // namespace univs

@@ -2,7 +2,7 @@
 catalog and the YTVOS api, and the folder walk of datasets/data_utils/custom_videos/convert_custom_videos_to_coco_test.py:61-78.
 
 Test mode only: the per-frame annotation lists of a record are empty.  The reference fills them from `segmentations` / `bboxes`, and its
-test mapper reads them only for task "sot" (first-frame masks), which is not built here."""
+test mapper reads them only for task "sot" (first-frame masks): those records come from vos_datasets.py."""
 import json
 import os
 
@@ -22,8 +22,10 @@ def task_and_name(dataset_name):
     if dataset_name.startswith("rvos"):                              # builtin.py:421-442: registered with has_expression=True
         return "grounding", dataset_name
     if dataset_name.startswith(_SOT_PREFIXES) or "sa_1b" in dataset_name:
-        raise NotImplementedError(f"task \"sot\" ({dataset_name}): the first frame's masks need the annotation transforms and a polygon "
-                                  "rasteriser, which are not built here")
+        if dataset_name.startswith(_SOT_PREFIXES):
+            raise NotImplementedError(f"task \"sot\" ({dataset_name}): data.load_vos_json (vos_datasets.py) reads the VOS data sets, with their "
+                                      "first-frame masks, and data.VOSTestMapper maps them")
+        raise NotImplementedError(f"task \"sot\" ({dataset_name}): SA-1B stores polygons, and no polygon rasteriser is built here")
     for prefix, name in _DETECTION_PREFIXES:
         if dataset_name.startswith(prefix):
             return "detection", name

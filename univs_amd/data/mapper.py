@@ -6,7 +6,8 @@ images); it needs no GPU.  resize="gpu" decodes on the host, uploads the frames 
 csrc/frame_resize.hip, which gives Pillow's bytes exactly (tests/test_frame_resize_gpu.py); `image` then stays on the device, where the
 drivers want it.  Sizes the kernel does not cover go through Pillow.
 
-Not built: task "sot" (first-frame annotations), raw video files, training -- each raises NotImplementedError and says which."""
+Task "sot" (first-frame annotations) has a mapper of its own, `VOSTestMapper` in vos_mapper.py; this one refuses it and says so.
+Not built: raw video files, training -- each raises NotImplementedError and says which."""
 import copy
 import glob
 import logging
@@ -116,13 +117,17 @@ class VideoTestMapper:
         return images
 
     def __call__(self, record):
+        if not record.get("is_raw_video") and record["task"] == "sot":
+            raise NotImplementedError("task \"sot\": this mapper reads no annotations; data.VOSTestMapper (vos_mapper.py) maps the records of "
+                                      "data.load_vos_json, first-frame masks included")
+        return self._map(record)
+
+    def _map(self, record):
+        """The mapper's dictionary of a record of any task, without per-frame annotations."""
         d = copy.deepcopy(record)
         if d.get("is_raw_video"):
             raise NotImplementedError(f"raw video input (video {d.get('video_id')}): torchvision.io is absent; convert the video to frames first")
         task = d["task"]
-        if task == "sot":
-            raise NotImplementedError("task \"sot\": the first frame's masks need the annotation transforms and a polygon rasteriser, which "
-                                      "are not built here")
         d.pop("annotations", None)
         file_names = d.pop("file_names")
         n = d["length"]

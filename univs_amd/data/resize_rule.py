@@ -10,6 +10,12 @@ formula divides by the scale; this file multiplies too (no integer coefficient d
 400, so the choice is caution, not a known difference).
 
 `shortest_edge_size` restates detectron2 (absent here), so it is not pinned to the reference's code, only to worked examples.
+
+Masks are resized with `PIL.Image.resize(..., NEAREST)` (detectron2's `ResizeTransform.apply_segmentation`).  Per axis Pillow walks
+a float64 source coordinate: a = n_in / n_out, xo = a / 2, and for every output index in turn src = int(xo), xo += a.  The sum is
+ACCUMULATED; the closed form floor((i + 0.5) a) is a different table (first at 2 -> 7) and not Pillow's.  `nearest_table` is that
+loop, `resize_nearest` the gather; csrc/mask_prompt_resize.hip takes the tables as arguments (tests/test_prompt_masks_rule_cpu.py pins
+them to Pillow itself and to tests/golden/g33_prompt_masks_pil.npz).
 """
 import math
 
@@ -93,3 +99,27 @@ def resize_u8_reference(a, newh, neww):
     if int(newh) != a.shape[0]:
         a = _pass(a, int(newh), 0)
     return np.ascontiguousarray(a)
+
+
+def nearest_table(n_in, n_out):
+    """int32 [n_out]: the source index of every output index of one axis under Pillow's NEAREST, by Pillow's own running sum in
+    float64 (not the closed form: see the module's docstring)."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"nearest_table: n_in={n_in} n_out={n_out}")
+    a = n_in / n_out
+    xo = a * 0.5
+    table = np.empty(n_out, np.int32)
+    for i in range(n_out):
+        table[i] = int(xo)
+        xo += a
+    return np.minimum(table, n_in - 1)                                # (never taken for a table Pillow accepts; a bound all the same)
+
+
+def resize_nearest(mask, newh, neww):
+    """[H, W(, C)] -> [newh, neww(, C)] of the same dtype: `PIL.Image.resize((neww, newh), NEAREST)` element for element."""
+    mask = np.asarray(mask)
+    if mask.ndim not in (2, 3):
+        raise ValueError(f"resize_nearest: [H, W(, C)], got {mask.shape}")
+    ty, tx = nearest_table(mask.shape[0], newh), nearest_table(mask.shape[1], neww)
+    return np.ascontiguousarray(mask[ty][:, tx])

@@ -99,8 +99,10 @@ def rle_encode_masks(masks: torch.Tensor) -> List[dict]:
 
 
 def rle_counts(rle: dict) -> np.ndarray:
-    """The run lengths stored in a compressed RLE string."""
+    """The run lengths stored in a compressed RLE string (an uncompressed list of counts is returned as it is)."""
     s = rle["counts"]
+    if isinstance(s, (list, tuple, np.ndarray)):
+        return np.asarray(s, dtype=np.int64).reshape(-1)
     s = s.decode("ascii") if isinstance(s, (bytes, bytearray)) else s
     out, p = [], 0
     while p < len(s):

@@ -1,12 +1,20 @@
 """`python -m univs_amd.run`: a checkpoint and frames on disk to result files.
 
     python -m univs_amd.run --config-file F --weights W (--json J --image-root R --dataset-name N | --video-dir D) --output-dir O
-                            [--resize gpu|host] [--gt-json G | --pan-gt-json P --truth-dir T] [KEY VALUE ...]
+                            [--resize gpu|host] [--gt-json G | --pan-gt-json P --truth-dir T | --davis-root V | --pvos-data V]
+                            [KEY VALUE ...]
 
 The model is `build_model(load_cfg(F, [KEY VALUE ...]))` with `ckpt["model"]` loaded strictly (the reference's state-dict layout).  The
 frames are the videos of a YouTube-VIS-format file, or the sub-folders of a folder of jpg / png frames (data/datasets.py), mapped by
 data.VideoTestMapper.  With --gt-json the outputs go to evaluation.YTVISEvaluator (results.json; AP / AR when the file has annotations),
 with --pan-gt-json and --truth-dir to evaluation.VPSEvaluator; without either each video's driver output is saved to O/<video_id>.pt.
+
+A --dataset-name of a video-object-segmentation data set (sot_*, mots_mose*, mots_burst*, pvos_*) reads the file with
+data.load_vos_json and maps it with data.VOSTestMapper, first-frame masks included.  The id maps the VOS driver returns per clip are
+written as palette PNGs to O/inference/Annotations/<video>/<frame>.png (`write_vos_outputs`); --davis-root V (the DAVIS folder that
+holds Annotations/ and ImageSets/) then scores them with evaluation.DAVISEvaluator in its semi-supervised task (davis-metrics.txt in
+O/inference), --pvos-data V (the VIPOSeg split folder) with evaluation.PVOSEvaluator (pvos-ious.txt); without either only the PNGs are
+written.
 """
 import argparse
 import json
@@ -16,8 +24,9 @@ import sys
 import torch
 
 from .config import load_cfg
-from .data import VideoTestMapper, load_video_json, video_records_from_dir
+from .data import VideoTestMapper, VOSTestMapper, is_vos_name, load_video_json, load_vos_json, video_records_from_dir
 from .engine import inference_on_videos
+from .inference.results import write_vos_pngs
 from .modeling.build import build_model
 
 
@@ -27,7 +36,7 @@ def parse_args(argv=None):
     ap.add_argument("--weights", required=True, help="a checkpoint whose \"model\" entry is the state dict")
     ap.add_argument("--json", help="a YouTube-VIS-format test file")
     ap.add_argument("--image-root", help="the folder the file names of --json are relative to")
-    ap.add_argument("--dataset-name", help="the registered name of --json's data set, e.g. ytvis_2021_val")
+    ap.add_argument("--dataset-name", help="the registered name of --json's data set, e.g. ytvis_2021_val or sot_davis17_val")
     ap.add_argument("--video-dir", help="a folder whose sub-folders hold the frames of one video each")
     ap.add_argument("--output-dir", required=True)
     ap.add_argument("--resize", choices=("gpu", "host"), default="gpu")
@@ -35,6 +44,8 @@ def parse_args(argv=None):
     ap.add_argument("--gt-json", help="YouTube-VIS annotation file: score with YTVISEvaluator")
     ap.add_argument("--pan-gt-json", help="VIPSeg panoptic ground-truth json: score with VPSEvaluator (with --truth-dir)")
     ap.add_argument("--truth-dir", help="the folder of the ground-truth panoptic PNGs")
+    ap.add_argument("--davis-root", help="the DAVIS folder (Annotations/, ImageSets/): score a sot_davis* run with DAVISEvaluator")
+    ap.add_argument("--pvos-data", help="the VIPOSeg split folder (Annotations/, meta files): score a pvos_* run with PVOSEvaluator")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="KEY VALUE pairs merged into the config")
     args = ap.parse_args(argv)
     from_json = args.json is not None
@@ -44,8 +55,15 @@ def parse_args(argv=None):
         ap.error("--json needs --image-root and --dataset-name")
     if (args.pan_gt_json is None) != (args.truth_dir is None):
         ap.error("--pan-gt-json and --truth-dir go together")
-    if args.gt_json and args.pan_gt_json:
-        ap.error("one evaluator at a time: --gt-json or --pan-gt-json")
+    if sum(v is not None for v in (args.gt_json, args.pan_gt_json, args.davis_root, args.pvos_data)) > 1:
+        ap.error("one evaluator at a time: --gt-json, --pan-gt-json, --davis-root or --pvos-data")
+    args.vos = bool(from_json and is_vos_name(args.dataset_name))
+    if (args.davis_root or args.pvos_data) and not args.vos:
+        ap.error("--davis-root and --pvos-data score a VOS data set (--dataset-name sot_*, mots_mose*, mots_burst*, pvos_*)")
+    if args.vos and (args.gt_json or args.pan_gt_json):
+        ap.error("a VOS data set is scored with --davis-root or --pvos-data")
+    if args.davis_root and not ("davis16" in args.dataset_name or "davis17" in args.dataset_name):
+        ap.error("--davis-root needs a davis16 / davis17 --dataset-name")
     return args
 
 
@@ -58,7 +76,37 @@ def build_evaluator(args):
         with open(args.pan_gt_json) as f:
             categories = {c["id"]: c for c in json.load(f)["categories"]}
         return VPSEvaluator(categories, args.pan_gt_json, args.truth_dir, args.output_dir, device=args.device)
+    # the two VOS evaluators read <their output_dir>/Annotations: the "inference" folder `write_vos_pngs` writes into
+    if getattr(args, "davis_root", None):
+        from .evaluation.davis import DAVISEvaluator      # (it takes the image root and drops two components: give them back)
+        return DAVISEvaluator(args.dataset_name, os.path.join(args.davis_root, "JPEGImages", "Full-Resolution"),
+                              output_dir=os.path.join(args.output_dir, "inference"), device=args.device)
+    if getattr(args, "pvos_data", None):
+        from .evaluation.pvos import PVOSEvaluator         # (likewise, one component)
+        return PVOSEvaluator(args.dataset_name, os.path.join(args.pvos_data, "JPEGImages"), distributed=False,
+                             output_dir=os.path.join(args.output_dir, "inference"), device=args.device)
     return None
+
+
+def vos_clip_offsets(n_clips, num_frames, clip_stride):
+    """The first frame of every clip's id maps.  `InferenceVideoVOS.inference_video_vos` starts clip c at frame c min(clip_stride,
+    num_frames), and `_finished_frames` returns that clip's maps from its first frame on.  The running sum of the maps' lengths is the
+    same number only while the stride is below the clip length: a clip that is not the last returns
+    `mask_logits[:, -T : min(-T + stride, -1)]`, which is `stride` frames for stride < T but T - 1 frames for stride == T -- the clip's
+    last frame is then in no clip's output (the reference's slice, inference_video_vos.py:640, kept as it is) and a running sum would
+    drift by one frame per clip.  So the offsets come from the schedule, not from the lengths."""
+    stride = min(int(clip_stride), int(num_frames))
+    return [c * stride for c in range(n_clips)]
+
+
+def write_vos_outputs(output_dir, inputs, outputs, num_frames, clip_stride):
+    """The per-clip id maps of one video ([T', H, W] uint8 each, `InferenceVideoVOS.save_vos_results`) -> the palette PNGs of
+    `results.write_vos_pngs`, each clip at its offset (`vos_clip_offsets`).  Returns the paths."""
+    video = inputs[0]
+    paths = []
+    for first, idmaps in zip(vos_clip_offsets(len(outputs), num_frames, clip_stride), outputs):
+        paths += write_vos_pngs(output_dir, video["file_names"], first, idmaps, video.get("mask_palette"))
+    return paths
 
 
 def main(argv=None):
@@ -68,18 +116,25 @@ def main(argv=None):
     ckpt = torch.load(args.weights, map_location="cpu")
     model.load_state_dict(ckpt["model"], strict=True)
     model = model.to(args.device)
-    if args.json:
+    if args.vos:
+        records = load_vos_json(args.json, args.image_root, args.dataset_name)
+    elif args.json:
         records = load_video_json(args.json, args.image_root, args.dataset_name)
     else:
         records = video_records_from_dir(args.video_dir)
-    mapper = VideoTestMapper.from_config(cfg, resize=args.resize, device=args.device)
+    mapper = (VOSTestMapper if args.vos else VideoTestMapper).from_config(cfg, resize=args.resize, device=args.device)
     os.makedirs(args.output_dir, exist_ok=True)
     evaluator = build_evaluator(args)
 
     def save(inputs, outputs):
         torch.save(outputs, os.path.join(args.output_dir, f"{inputs[0]['video_id']}.pt"))
 
-    results = inference_on_videos(model, records, mapper, evaluator, on_output=None if evaluator is not None else save)
+    def save_vos(inputs, outputs):
+        vos = model.inference_video_vos
+        write_vos_outputs(args.output_dir, inputs, outputs, vos.num_frames, vos.clip_stride)
+
+    on_output = save_vos if args.vos else (None if evaluator is not None else save)
+    results = inference_on_videos(model, records, mapper, evaluator, on_output=on_output)
     if evaluator is not None:
         print(json.dumps(results, default=str))
     return 0
