@@ -9,6 +9,7 @@
 #include "../../include/univs_eval_hip.h"
 #include "../../include/univs_frames_hip.h"
 #include "../../include/univs_fused_hip.h"
+#include "../../include/univs_png_hip.h"
 #include "../../include/univs_prompts_hip.h"
 #include "../../include/univs_pvos_hip.h"
 #include "../../include/univs_semantic_hip.h"
@@ -955,6 +956,19 @@ int univs_resize_rle_masks_u8(const int32_t* bounds, const int32_t* starts, long
   if (!bounds || !starts || !ty || !tx || !masks || !boxes) return e.null_pointer();
   return e.covered(resize_rle_masks_u8(bounds, starts, n_bounds, N, H, W, ty, tx, Ho, Wo, masks, boxes, e.st),
                    "not covered (H W < 2^31, n_bounds < 2^31, N Ho Wo < 2^31)");
+}
+
+// (include/univs_png_hip.h)
+int univs_png_deflate_maps(const void* src, int src_is_i32, int N, int H, int W, const uint8_t* lut, int K, int C, int rows_per_stripe,
+                           uint8_t* scratch, uint8_t* out, long long* offsets, void* stream) {
+  const Entry e("univs_png_deflate_maps", stream);
+  if (N < 0 || H < 1 || W < 1 || C < 1 || rows_per_stripe < 1 || (lut && K < 1) || (!lut && (src_is_i32 || C != 1)))
+    return e.invalid("bad arguments src_is_i32=%d N=%d H=%d W=%d lut=%s K=%d C=%d rows_per_stripe=%d", src_is_i32, N, H, W,
+                     lut ? "given" : "NULL", K, C, rows_per_stripe);
+  if (N == 0) return UNIVS_OK;
+  if (!src || !scratch || !out || !offsets) return e.null_pointer();
+  return e.covered(png_deflate_maps(src, src_is_i32, N, H, W, lut, K, C, rows_per_stripe, scratch, out, offsets, e.st),
+                   "not covered (C in {1, 3}, rows_per_stripe (W C + 1) <= 24576, N H (W C + 1) < 2^31)");
 }
 
 // The two window-attention entries on image-layout operands share their checks

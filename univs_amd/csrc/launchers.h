@@ -232,4 +232,8 @@ int resize_frames_u8(const unsigned char* src, int T, int Hi, int Wi, int Ho, in
 int resize_rle_masks_u8(const int* bounds, const int* starts, long long n_bounds, int N, int H, int W, const int* ty, const int* tx, int Ho,
                         int Wo, unsigned char* masks, int* boxes, hipStream_t st);
 
+// ---- png_deflate.hip: returns UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the sizes are not covered, or the launch's error
+int png_deflate_maps(const void* src, int src_is_i32, int N, int H, int W, const unsigned char* lut, int K, int C, int rows_per_stripe,
+                     unsigned char* scratch, unsigned char* out, long long* offsets, hipStream_t st);
+
 }  // namespace univs

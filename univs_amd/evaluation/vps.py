@@ -472,9 +472,10 @@ class VPSEvaluator:
     video's ground-truth PNGs are there it also counts the video's pair tables at once, from the int32 `pred_masks` it was handed: the
     table's columns are moved from segment ids to the colour ids of the record it just wrote.  `evaluate` then reads no predicted PNG."""
 
-    def __init__(self, categories, pan_gt_json_file, truth_dir, output_dir, device=None):
+    def __init__(self, categories, pan_gt_json_file, truth_dir, output_dir, device=None, png="host"):
         self.categories, self.pan_gt_json_file, self.truth_dir, self._output_dir, self.device = categories, pan_gt_json_file, truth_dir, output_dir, device
         self._gt_jsons = None
+        self.png = png                                               # ("host" | "gpu": who compresses the PNGs, results.py)
         self.reset()
 
     def _gt(self):
@@ -490,7 +491,7 @@ class VPSEvaluator:
     def process(self, inputs, outputs):
         from ..inference.results import write_vps_predictions
         assert len(inputs) == 1, "More than one inputs are loaded for inference!"
-        record = write_vps_predictions(inputs[0], outputs, self._output_dir, self.categories)
+        record = write_vps_predictions(inputs[0], outputs, self._output_dir, self.categories, png=self.png)
         self._predictions.append(record)
         tables = self._tables_in_process(record, outputs)
         if tables is not None:

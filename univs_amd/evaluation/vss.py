@@ -182,11 +182,12 @@ class VSSEvaluator:
     in the video's mask directory, it also counts the video at once from the tensor it was handed and the ground-truth masks; `evaluate`
     then reads no PNG of that video.  Any other video of the split is scored from the files."""
 
-    def __init__(self, contiguous_id_to_dataset_id, ignore_val, num_classes, data_dir, split_file, output_dir, device=None, eval_miou_res=-1):
+    def __init__(self, contiguous_id_to_dataset_id, ignore_val, num_classes, data_dir, split_file, output_dir, device=None, eval_miou_res=-1, png="host"):
         if eval_miou_res > 0:
             raise NotImplementedError("eval_miou_res > 0 rescales the ground truth with mmcv, which the reference's evaluator does not import")
         self.contiguous_id_to_dataset_id, self.ignore_val, self.num_classes = dict(contiguous_id_to_dataset_id), ignore_val, int(num_classes)
         self.data_dir, self.split_file, self._output_dir, self.device = data_dir, split_file, output_dir, device
+        self.png = png                                               # ("host" | "gpu": who compresses the PNGs, results.py)
         self.reset()
 
     def reset(self):
@@ -196,7 +197,7 @@ class VSSEvaluator:
     def process(self, inputs, outputs):
         from ..inference.results import write_vss_predictions
         assert len(inputs) == 1, "More than one inputs are loaded for inference!"
-        paths = write_vss_predictions(inputs[0], outputs, self._output_dir, self.contiguous_id_to_dataset_id, self.ignore_val)
+        paths = write_vss_predictions(inputs[0], outputs, self._output_dir, self.contiguous_id_to_dataset_id, self.ignore_val, png=self.png)
         self._processed += 1
         video = str(inputs[0]["video_id"])
         self._counts.pop(video, None)

@@ -13,6 +13,12 @@
                                                   colour-coded panoptic maps + the `pred.json` segment records that VPQ / STQ read
     write_vss_predictions                         univs/evaluation/vss_evaluation.py:93-118    VSPW layout: `<video>/<frame>.png` class ids
 
+The four PNG writers take `png="host"` (the default: the planes are downloaded and `PIL.Image.save` compresses each on a host core)
+or `png="gpu"`: the maps stay on the device, csrc/png_deflate.hip emits every frame's zlib stream (png_ops.deflate_maps; the colours
+of a panoptic map and the class remap of a semantic map are its look-up table), and the host only wraps the streams in chunks
+(png_rule.png_file).  Same paths, same return values, files that decode to the same pixels, mode and palette; where the kernels do
+not cover a size the frames are saved with Pillow.
+
 pycocotools is a third-party dependency of the reference (un-pinned: INSTALL.md installs the latest release) and is absent
 from this image, so the RLE string coding is restated from its published algorithm (`rleToString` / `rleFrString` in
 maskApi.c: 5 payload bits + continuation bit per character, offset 48, counts after the third stored as differences to the
@@ -223,12 +229,51 @@ def _png_name(file_name: str) -> str:
     return file_name.split("/")[-1].replace(".jpg", ".png")
 
 
-def write_vos_pngs(output_dir: str, file_names: Sequence[str], first_frame_idx: int, idmaps: torch.Tensor, palette=None):
+def _png_mode(png):
+    if png not in ("host", "gpu"):
+        raise ValueError(f'png="{png}": "host" or "gpu"')
+    return png == "gpu"
+
+
+def _on_device(maps, dtype):
+    """The maps as a contiguous `dtype` tensor on the GPU: uploaded if they came as a CPU tensor or an array."""
+    t = maps if isinstance(maps, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(maps))
+    return t.to(device=t.device if t.is_cuda else "cuda", dtype=dtype).contiguous()
+
+
+def _write_gpu_pngs(paths, ids, lut=None, channels=1, palette=None):
+    """One PNG per frame of the device id maps [N, H, W] at `paths`: the zlib streams from the device, the chunks from the host.  Where
+    the kernels do not cover the size: Pillow, frame by frame, on the looked-up planes."""
+    from .. import png_ops
+    if lut is not None:
+        lut = torch.from_numpy(np.ascontiguousarray(lut, dtype=np.uint8).reshape(-1, channels)).to(ids.device)
+    streams = png_ops.deflate_maps(ids, lut, channels)
+    H, W = int(ids.shape[1]), int(ids.shape[2])
+    if streams is not None:
+        for path, data in zip(paths, png_ops.png_files(streams, H, W, channels, palette)):
+            with open(path, "wb") as f:
+                f.write(data)
+        return
+    from PIL import Image
+    for path, m in zip(paths, ids):
+        m = m if lut is None else lut[m.long().clamp(0, lut.shape[0] - 1)]
+        img = Image.fromarray(m.cpu().numpy().reshape((H, W) if channels == 1 else (H, W, channels)))
+        if palette is not None:
+            img.putpalette(palette)
+        img.save(path)
+        img.close()
+
+
+def write_vos_pngs(output_dir: str, file_names: Sequence[str], first_frame_idx: int, idmaps: torch.Tensor, palette=None, png="host"):
     """`InferenceVideoVOS.save_vos_results` output ([T', H, W] uint8 object ids) -> palette PNGs
     `<output_dir>/inference/Annotations/<video>/<frame>.png`, the layout the DAVIS / YouTube-VOS servers expect."""
     from PIL import Image
     save_dir = os.path.join(output_dir, "inference/Annotations", file_names[0].split("/")[-2])
     os.makedirs(save_dir, exist_ok=True)
+    if _png_mode(png):
+        paths = [os.path.join(save_dir, _png_name(file_names[first_frame_idx + t])) for t in range(len(idmaps))]
+        _write_gpu_pngs(paths, _on_device(idmaps, torch.uint8), palette=palette)
+        return paths
     paths = []
     for t, m in enumerate(idmaps.cpu().numpy().astype(np.uint8)):
         img = Image.fromarray(m)
@@ -240,12 +285,21 @@ def write_vos_pngs(output_dir: str, file_names: Sequence[str], first_frame_idx: 
     return paths
 
 
-def write_rvos_pngs(output_dir: str, file_names: Sequence[str], first_frame_idx: int, result: dict):
+def write_rvos_pngs(output_dir: str, file_names: Sequence[str], first_frame_idx: int, result: dict, png="host"):
     """`InferenceVideoVOS.save_rvos_results` output ({"ids", "masks" [N, T', H, W] uint8 0/255}) -> grey PNGs
     `<output_dir>/inference/Annotations/<video>/<expression id>/<frame>.png` (Ref-YouTube-VOS / Ref-DAVIS layout)."""
     from PIL import Image
     video = file_names[0].split("/")[-2]
     paths = []
+    if _png_mode(png):
+        masks = _on_device(result["masks"], torch.uint8)             # all expressions' frames in one call
+        for id_ in result["ids"][:len(masks)]:
+            save_dir = os.path.join(output_dir, "inference/Annotations", video, str(id_))
+            os.makedirs(save_dir, exist_ok=True)
+            paths += [os.path.join(save_dir, _png_name(file_names[first_frame_idx + t])) for t in range(masks.shape[1])]
+        if paths:
+            _write_gpu_pngs(paths, masks[:len(result["ids"])].reshape(-1, *masks.shape[2:]))
+        return paths
     for id_, mi in zip(result["ids"], result["masks"].cpu().numpy().astype(np.uint8)):
         save_dir = os.path.join(output_dir, "inference/Annotations", video, str(id_))
         os.makedirs(save_dir, exist_ok=True)
@@ -300,7 +354,63 @@ class IdGenerator:
                 return color
 
 
-def write_vps_predictions(inputs: dict, outputs: dict, output_dir: str, categories: dict):
+def _vps_segment_records(pan, seg_ids):
+    """Per listed segment and frame (area, x0, y0, x1, y1) of the pixels pan == id, on pan's device: int64 numpy [S, T, 5]; the area is 0
+    where the segment has no pixel in the frame.  What the host writer's `np.where` loop gives, from min / max over two masked planes."""
+    T, H, W = pan.shape
+    if not len(seg_ids):
+        return np.zeros((0, T, 5), dtype=np.int64)
+    ys = torch.arange(H, device=pan.device).view(1, H, 1)
+    xs = torch.arange(W, device=pan.device).view(1, 1, W)
+    recs = []
+    for sid in seg_ids:
+        m = pan == sid
+        recs.append(torch.stack([m.sum((1, 2)), torch.where(m, xs, W).amin((1, 2)), torch.where(m, ys, H).amin((1, 2)),
+                                 torch.where(m, xs, -1).amax((1, 2)), torch.where(m, ys, -1).amax((1, 2))], dim=1))
+    return torch.stack(recs).cpu().numpy()                              # (one download for all segments)
+
+
+def _write_vps_predictions_gpu(inputs, outputs, output_dir, categories):
+    """write_vps_predictions with the maps kept on the device: the colours of `segments_infos`' order are the encoder's look-up table
+    (a later entry of the same id wins, as the host's repeated painting), areas and boxes come from torch on the device."""
+    color_generator = IdGenerator(categories)
+    image_names = [inputs["file_names"][int(i)] for i in inputs["frame_indices"]]
+    video_id = image_names[0].split("/")[-2]
+    H, W = int(outputs["image_size"][0]), int(outputs["image_size"][1])
+    pan = _on_device(outputs["pred_masks"], torch.int64)
+    if tuple(pan.shape[1:]) != (H, W):
+        raise ValueError(f"pred_masks {tuple(pan.shape)} against image_size {(H, W)}")
+    infos = outputs["segments_infos"]
+    colors = [color_generator.get_color(info["category_id"]) for info in infos]
+    # ids -> rows of the table: row 0 is "no listed segment" (black), row k + 1 the k-th distinct listed id
+    listed = sorted({int(info["id"]) for info in infos})
+    lut = np.zeros((len(listed) + 1, 3), dtype=np.uint8)
+    for info, color in zip(infos, colors):
+        lut[1 + listed.index(int(info["id"]))] = color
+    if listed:
+        keys = torch.tensor(listed, dtype=torch.int64, device=pan.device)
+        pos = torch.searchsorted(keys, pan).clamp(max=len(listed) - 1)
+        rows = torch.where(keys[pos] == pan, pos + 1, 0).to(torch.int32)
+    else:
+        rows = torch.zeros_like(pan, dtype=torch.int32)
+    stats = _vps_segment_records(pan, [int(info["id"]) for info in infos])
+    save_dir = os.path.join(output_dir, "pan_pred", video_id)
+    os.makedirs(save_dir, exist_ok=True)
+    _write_gpu_pngs([os.path.join(save_dir, name.split("/")[-1].split(".")[0] + ".png") for name in image_names][:len(rows)],
+                    rows[:len(image_names)].contiguous(), lut, channels=3)
+    annotations = []
+    for i, name in enumerate(image_names):
+        segs = []
+        for k, (info, color) in enumerate(zip(infos, colors)):
+            area, x0, y0, x1, y1 = (int(v) for v in stats[k, i])
+            if area:
+                segs.append({"bbox": [x0, y0, x1 - x0, y1 - y0], "area": area, "category_id": int(info["category_id"]) - 1, "iscrowd": 0,
+                             "id": int(rgb2id(color))})
+        annotations.append({"segments_info": segs, "file_name": name.split("/")[-1]})
+    return {"annotations": annotations, "video_id": video_id}
+
+
+def write_vps_predictions(inputs: dict, outputs: dict, output_dir: str, categories: dict, png="host"):
     """One video's `vps_output_results` dict ({"image_size", "pred_masks" [T, H, W] segment ids, "segments_infos": [{"id", "isthing",
     "category_id"}]}) -> `<output_dir>/pan_pred/<video>/<frame>.png` (RGB panoptic maps) and the video's record for `pred.json`:
     {"annotations": [{"segments_info": [{"bbox", "area", "category_id", "iscrowd", "id"}], "file_name"}], "video_id"} -- what
@@ -308,6 +418,8 @@ def write_vps_predictions(inputs: dict, outputs: dict, output_dir: str, categori
     there).  `inputs`: the batched input of the video ("file_names", "frame_indices"); `categories`: {category id: {"id", "isthing",
     "color"}} (the dataset metadata's `categories`)."""
     from PIL import Image
+    if _png_mode(png):
+        return _write_vps_predictions_gpu(inputs, outputs, output_dir, categories)
     color_generator = IdGenerator(categories)
     image_names = [inputs["file_names"][int(i)] for i in inputs["frame_indices"]]
     video_id = image_names[0].split("/")[-2]
@@ -354,13 +466,29 @@ def write_vps_json(predictions: Sequence[dict], output_dir: str) -> str:
     return path
 
 
-def write_vss_predictions(inputs: dict, outputs: dict, output_dir: str, contiguous_id_to_dataset_id: dict, ignore_val: int = 255):
+def write_vss_predictions(inputs: dict, outputs: dict, output_dir: str, contiguous_id_to_dataset_id: dict, ignore_val: int = 255,
+                          png="host"):
     """One video's `vss_output_results` dict ({"image_size", "pred_masks" [T, H, W] contiguous class ids}) -> `<output_dir>/<video_id>/
     <frame>.png`, uint8 class ids as VSPW's evaluation reads them: the dataset id of the class minus the smallest dataset id, 255 where
     the prediction is the ignore value (`VSSEvaluator.process`, univs/evaluation/vss_evaluation.py:93-118)."""
     from PIL import Image
     video_id = str(inputs["video_id"])
     image_names = [inputs["file_names"][int(i)] for i in inputs["frame_indices"]]
+    if _png_mode(png):
+        # the class ids as bytes (the host's `astype(np.uint8)`), the remap as the encoder's table: a class that is predicted and has
+        # no dataset id is the host's KeyError, raised here from the ids present
+        sem = _on_device(outputs["pred_masks"], torch.uint8)
+        assert len(image_names) == len(sem), "Mismatch length between predicted and gt images"
+        lo = min(contiguous_id_to_dataset_id.values())
+        lut = np.full(256, 255, dtype=np.uint8)
+        for cls_id in torch.unique(sem).tolist():
+            if cls_id != ignore_val:
+                lut[cls_id] = np.uint8((contiguous_id_to_dataset_id[int(cls_id)] - lo) % 256)
+        save_dir = os.path.join(output_dir, video_id)
+        os.makedirs(save_dir, exist_ok=True)
+        paths = [os.path.join(save_dir, name.split("/")[-1].split(".")[0] + ".png") for name in image_names]
+        _write_gpu_pngs(paths, sem, lut, channels=1)
+        return paths
     sem = outputs["pred_masks"]
     sem = (sem.cpu().numpy() if isinstance(sem, torch.Tensor) else np.asarray(sem)).astype(np.uint8)
     out = np.full_like(sem, 255, dtype=np.uint8)

@@ -1,7 +1,8 @@
 """`python -m univs_amd.run`: a checkpoint and frames on disk to result files.
 
     python -m univs_amd.run --config-file F --weights W (--json J --image-root R --dataset-name N | --video-dir D) --output-dir O
-                            [--resize gpu|host] [--gt-json G | --pan-gt-json P --truth-dir T | --davis-root V | --pvos-data V]
+                            [--resize gpu|host] [--png host|gpu]
+                            [--gt-json G | --pan-gt-json P --truth-dir T | --davis-root V | --pvos-data V]
                             [KEY VALUE ...]
 
 The model is `build_model(load_cfg(F, [KEY VALUE ...]))` with `ckpt["model"]` loaded strictly (the reference's state-dict layout).  The
@@ -15,6 +16,9 @@ written as palette PNGs to O/inference/Annotations/<video>/<frame>.png (`write_v
 holds Annotations/ and ImageSets/) then scores them with evaluation.DAVISEvaluator in its semi-supervised task (davis-metrics.txt in
 O/inference), --pvos-data V (the VIPOSeg split folder) with evaluation.PVOSEvaluator (pvos-ious.txt); without either only the PNGs are
 written.
+
+--png gpu has the result PNGs (the VOS id maps, the VPS panoptic maps) compressed on the device by csrc/png_deflate.hip instead of by
+Pillow on a host core: the same paths and the same pixels, mode and palette, other (larger) files; the default is host.
 """
 import argparse
 import json
@@ -40,6 +44,7 @@ def parse_args(argv=None):
     ap.add_argument("--video-dir", help="a folder whose sub-folders hold the frames of one video each")
     ap.add_argument("--output-dir", required=True)
     ap.add_argument("--resize", choices=("gpu", "host"), default="gpu")
+    ap.add_argument("--png", choices=("host", "gpu"), default="host", help="who compresses the result PNGs: Pillow, or the HIP encoder")
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--gt-json", help="YouTube-VIS annotation file: score with YTVISEvaluator")
     ap.add_argument("--pan-gt-json", help="VIPSeg panoptic ground-truth json: score with VPSEvaluator (with --truth-dir)")
@@ -75,7 +80,8 @@ def build_evaluator(args):
         from .evaluation.vps import VPSEvaluator
         with open(args.pan_gt_json) as f:
             categories = {c["id"]: c for c in json.load(f)["categories"]}
-        return VPSEvaluator(categories, args.pan_gt_json, args.truth_dir, args.output_dir, device=args.device)
+        return VPSEvaluator(categories, args.pan_gt_json, args.truth_dir, args.output_dir, device=args.device,
+                            png=getattr(args, "png", "host"))
     # the two VOS evaluators read <their output_dir>/Annotations: the "inference" folder `write_vos_pngs` writes into
     if getattr(args, "davis_root", None):
         from .evaluation.davis import DAVISEvaluator      # (it takes the image root and drops two components: give them back)
@@ -99,13 +105,13 @@ def vos_clip_offsets(n_clips, num_frames, clip_stride):
     return [c * stride for c in range(n_clips)]
 
 
-def write_vos_outputs(output_dir, inputs, outputs, num_frames, clip_stride):
+def write_vos_outputs(output_dir, inputs, outputs, num_frames, clip_stride, png="host"):
     """The per-clip id maps of one video ([T', H, W] uint8 each, `InferenceVideoVOS.save_vos_results`) -> the palette PNGs of
     `results.write_vos_pngs`, each clip at its offset (`vos_clip_offsets`).  Returns the paths."""
     video = inputs[0]
     paths = []
     for first, idmaps in zip(vos_clip_offsets(len(outputs), num_frames, clip_stride), outputs):
-        paths += write_vos_pngs(output_dir, video["file_names"], first, idmaps, video.get("mask_palette"))
+        paths += write_vos_pngs(output_dir, video["file_names"], first, idmaps, video.get("mask_palette"), png=png)
     return paths
 
 
@@ -131,7 +137,7 @@ def main(argv=None):
 
     def save_vos(inputs, outputs):
         vos = model.inference_video_vos
-        write_vos_outputs(args.output_dir, inputs, outputs, vos.num_frames, vos.clip_stride)
+        write_vos_outputs(args.output_dir, inputs, outputs, vos.num_frames, vos.clip_stride, png=args.png)
 
     on_output = save_vos if args.vos else (None if evaluator is not None else save)
     results = inference_on_videos(model, records, mapper, evaluator, on_output=on_output)
