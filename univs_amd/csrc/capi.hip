@@ -17,6 +17,7 @@
 #include "common.h"
 #include "config.h"
 #include "launchers.h"
+#include "pair_xres_plan.h"
 
 namespace univs {
 
@@ -325,8 +326,14 @@ int univs_encoder_linear_pair_presplit_f32(const float* x, const float* add, lon
     return e.invalid("bad arguments M=%lld K=%d add_rows=%lld rows_per_batch=%lld N_a=%d col_block_a=%d N_b=%d col_block_b=%d", M, K, add_rows,
                      rows_per_batch, N_a, col_block_a, N_b, col_block_b);
   if (!x || !add || !wp_a || !winv_a || !y_a || !wp_b || !winv_b || !y_b) return e.null_pointer();
-  return e.launched(linear_pair_f16x3_f32(x, add, add_rows, wp_a, winv_a, bias_a, N_a, col_block_a, y_a, wp_b, winv_b, bias_b, N_b, col_block_b,
-                                          y_b, M, K, rows_per_batch, e.st),
+  // the x-resident kernel where it covers the call (linear_pair_xres.hip; UnivsConfig.linear_ablate == 11 switches it off: A / B), else the
+  // W-resident pass kernel -- bit-identical results, and the same coverage of the entry as before
+  int rc = linear_pair_xres_f32(x, add, add_rows, wp_a, winv_a, bias_a, N_a, col_block_a, y_a, wp_b, winv_b, bias_b, N_b, col_block_b, y_b, M, K,
+                                rows_per_batch, e.st);
+  if (rc == 0)
+    rc = linear_pair_f16x3_f32(x, add, add_rows, wp_a, winv_a, bias_a, N_a, col_block_a, y_a, wp_b, winv_b, bias_b, N_b, col_block_b, y_b, M, K,
+                               rows_per_batch, e.st);
+  return e.launched(rc,
                     "not covered (K == 256, add_rows == rows_per_batch dividing M, N_a in passes of 113 .. 128 features and N_b of 81 .. 96, "
                     "column blocks of a multiple of 4 dividing N, 16-byte aligned pointers, M max(K, N_a, N_b) 4 < 2^31)");
 }
