@@ -479,12 +479,16 @@ static int gs_conv(const float* x, const void* wp, const float* winv, const floa
 
 int conv3x3_f16x3_f32(const float* x, const void* wp, const float* winv, float* y, int T, int Cin, int Cout, int H, int W,
                       hipStream_t st) {
+  // all 256 output features on one read of x where that kernel covers the call (conv3x3_wide.hip; UnivsConfig.linear_ablate == 12
+  // switches it off: A / B), else the passes of 128 features; the same bits either way
+  if (const int rc = conv3x3_wide_f32(1, x, wp, winv, y, T, Cin, Cout, H, W, st); rc != 0) return rc == 1 ? UNIVS_OK : rc;
   return gs_conv<1>(x, wp, winv, nullptr, y, T, Cin, Cout, H, W, 9, st);
 }
 
 // the same convolution on a CHANNELS-LAST operand (output NCHW as above)
 int conv3x3_nhwc_f16x3_f32(const float* x, const void* wp, const float* winv, float* y, int T, int Cin, int Cout, int H, int W,
                            hipStream_t st) {
+  if (const int rc = conv3x3_wide_f32(2, x, wp, winv, y, T, Cin, Cout, H, W, st); rc != 0) return rc == 1 ? UNIVS_OK : rc;
   return gs_conv<2>(x, wp, winv, nullptr, y, T, Cin, Cout, H, W, 9, st);
 }
 

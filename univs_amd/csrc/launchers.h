@@ -72,6 +72,10 @@ int conv1x1_f16x3_f32(const float* x, const void* wp, const float* winv, const f
 int conv1x1_fused_f16x3_f32(const float* x, int channels_last, const float* affine, const void* wp, const float* winv, const float* bias,
                             float* y, int T, int Cin, int Cout, int H, int W, hipStream_t st);
 
+// ---- conv3x3_wide.hip: returns 1 if launched, 0 if not covered (or switched off), < 0 on error.  xmode 1: x [T, Cin, H, W]; 2: x [T, H, W, Cin]
+int conv3x3_wide_f32(int xmode, const float* x, const void* wp, const float* winv, float* y, int T, int Cin, int Cout, int H, int W,
+                     hipStream_t st);
+
 // ---- gemm_f16x3_tile.hip: returns UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the shape or alignment is not covered, or the launch's error
 int linear_f16x3_tile_f32(const float* x, const void* wp, const float* winv, const float* bias, const float* residual, float* y,
                           long long M, int N, int K, int epi, hipStream_t st);
