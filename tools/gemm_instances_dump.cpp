@@ -35,10 +35,10 @@ static void resident(char* out, size_t n, long long M, int N, int K, int epi, in
   else snprintf(out, n, "linear_f16x3<%d,%d,%d>", p.RB, p.ring, pre ? 1 : 0);
 }
 
-// univs_linear_presplit_f32 (capi.hip): linear_f16x3_tile_f32 unless linear_ablate == 6 or not covered, then linear_f16x3_stream_f32
+// univs_linear_presplit_f32 (capi.hip): linear_f16x3_tile_f32 unless linear_ablate == LA_NO_TILE or not covered, then linear_f16x3_stream_f32
 static void presplit(char* out, size_t n, long long M, int N, int K, const UnivsConfig& cfg, int n_cu) {
   snprintf(out, n, "not covered");
-  if (cfg.linear_ablate != 6) {
+  if (cfg.linear_ablate != univs::LA_NO_TILE) {
     const TilePlan t = plan_tile(M, N, K, n_cu, cfg);
     if (t.covered) {
       // the launcher's switch: two workgroups per CU only for the tiles built with them, then two load slots
@@ -79,8 +79,8 @@ static void mlp(char* out, size_t n, long long M, int C, int Hd, int act, int ab
   const int ks1 = C / 32;
   if ((size_t)(db ? 2 : 1) * 16 * C * 16 + (size_t)(2 * Hd + 6 * C) * 4 > 160 * 1024) return;
   int abl = 0;
-  if (ablate >= 2 && ablate <= 4 && ((ks1 == 8 && act == 1) || (ks1 == 3 && act == 2))) abl = ablate - 1;
-  if (abl == 0 && ablate == 10 && db && nw == 8 && ct == 1 && ks1 >= 4 && (size_t)4 * 8 * C * 16 + (size_t)(2 * Hd + 6 * C) * 4 <= 160 * 1024) {
+  if (ablate >= univs::LA_MLP_NOMFMA && ablate <= univs::LA_MLP_NOACT && ((ks1 == 8 && act == 1) || (ks1 == 3 && act == 2))) abl = ablate - 1;
+  if (abl == 0 && ablate == univs::LA_MLP_PHASE_SHIFT && db && nw == 8 && ct == 1 && ks1 >= 4 && (size_t)4 * 8 * C * 16 + (size_t)(2 * Hd + 6 * C) * 4 <= 160 * 1024) {
     snprintf(out, n, "mlp_f16x3_ps<%d,%d>", ks1, act);
     return;
   }

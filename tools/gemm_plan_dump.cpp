@@ -248,7 +248,8 @@ int main() {
       for (int K : {448, 768, 3072}) linear("edge tile occupancy", c, L, M, K, N);
   // UnivsConfig.linear_rows_per_pass / linear_grid_x / linear_ablate
   const int cfgs[][3] = {{15, 0, 0}, {16, 0, 0}, {64, 0, 0}, {100, 0, 0}, {128, 0, 0}, {192, 0, 0}, {256, 0, 0}, {0, 3, 0}, {0, 4, 0},
-                         {0, 5, 0}, {0, 40, 0}, {0, 100000, 0}, {192, 4, 0}, {0, 0, 5}, {0, 0, 6}, {0, 0, 7}, {0, 0, 8}, {0, 0, 9}};
+                         {0, 5, 0}, {0, 40, 0}, {0, 100000, 0}, {192, 4, 0}, {0, 0, LA_NO_XCD_REMAP}, {0, 0, LA_NO_TILE}, {0, 0, LA_TILE_NSLOT2}, {0, 0, LA_TILE_NSLOT3},
+                         {0, 0, LA_TILE_NSLOT4}};
   for (auto& g : cfgs) {
     char l[80];
     snprintf(l, sizeof(l), "config rows_per_pass=%d grid_x=%d ablate=%d", g[0], g[1], g[2]);

@@ -289,12 +289,12 @@ int univs_small_mlp_presplit_f32(const float* x, int stages, const void* const* 
 
 int univs_linear_presplit_f32(const float* x, const void* wp, const float* winv, const float* bias, const float* residual,
                               long long M, int N, int K, int act, float* y, void* stream) {
-  // the two-dimensional tiling where it applies (gemm_f16x3_tile.hip; UnivsConfig.linear_ablate == 6 switches it off: A / B), else the
+  // the two-dimensional tiling where it applies (gemm_f16x3_tile.hip; UnivsConfig.linear_ablate == LA_NO_TILE switches it off: A / B), else the
   // row-range x pass kernel -- bit-identical results
   const Entry e("univs_linear_presplit_f32", stream);
   return linear_entry(e, M, N, K, act, residual, x && wp && winv && y, /*resident=*/false, [&](int epi) {
     int rc = UNIVS_ERR_NOT_IMPLEMENTED;
-    if (config().linear_ablate != 6) rc = linear_f16x3_tile_f32(x, wp, winv, bias, residual, y, M, N, K, epi, e.st);
+    if (config().linear_ablate != LA_NO_TILE) rc = linear_f16x3_tile_f32(x, wp, winv, bias, residual, y, M, N, K, epi, e.st);
     if (rc == UNIVS_ERR_NOT_IMPLEMENTED) rc = linear_f16x3_stream_f32(x, wp, winv, bias, residual, y, M, N, K, epi, e.st);
     return rc;
   });
@@ -326,7 +326,7 @@ int univs_encoder_linear_pair_presplit_f32(const float* x, const float* add, lon
     return e.invalid("bad arguments M=%lld K=%d add_rows=%lld rows_per_batch=%lld N_a=%d col_block_a=%d N_b=%d col_block_b=%d", M, K, add_rows,
                      rows_per_batch, N_a, col_block_a, N_b, col_block_b);
   if (!x || !add || !wp_a || !winv_a || !y_a || !wp_b || !winv_b || !y_b) return e.null_pointer();
-  // the x-resident kernel where it covers the call (linear_pair_xres.hip; UnivsConfig.linear_ablate == 11 switches it off: A / B), else the
+  // the x-resident kernel where it covers the call (linear_pair_xres.hip; UnivsConfig.linear_ablate == LA_NO_PAIR_XRES switches it off: A / B), else the
   // W-resident pass kernel -- bit-identical results, and the same coverage of the entry as before
   int rc = linear_pair_xres_f32(x, add, add_rows, wp_a, winv_a, bias_a, N_a, col_block_a, y_a, wp_b, winv_b, bias_b, N_b, col_block_b, y_b, M, K,
                                 rows_per_batch, e.st);

@@ -12,13 +12,13 @@
 //     features, so the lead in time is that of the streamed kernel's four;
 //   * A fragments in eight batches of two feature blocks, two buffers (32 registers), read one batch ahead (f16x3_kstep.h);
 //   * W: a k-step's 256-feature slab is 32 contiguous KB of the pre-split image (units (kc 2 + part) N + r).  It goes global -> LDS by DMA
-//     (the stream of linear_pair_xres.hip) into four images = two PAIRS of k-steps: one barrier per pair, behind it the pair after
+//     (l3_glds16 of f16x3_wstream.h) into four images = two PAIRS of k-steps: one barrier per pair, behind it the pair after
 //     this one is requested into the images the pair before has left.  (One barrier per k-step with the k-step three ahead requested
 //     measured 25-40 us more on the NCHW operand: two waves of a SIMD that meet at every k-step do their vector work, and then their
 //     matrix work, at the same time.)  The ring runs on across tiles and rounds (the same W for every row: k-step indices wrap).
 // ARITHMETIC: an output's value depends on its row of W, its row of x in k order and that row's running-scale sequence only
 // (linear_pair_xres.hip); all three are the streamed kernel's -- the same l3_* helpers, the lowering vote over the same 32 rows, the
-// three products smallest first -- so y has the bits of gemm_f16x3_stream<8, 4, XMODE> (tests/test_conv3x3_wide_gpu.py).
+// three products in f16x3.h's order -- so y has the bits of gemm_f16x3_stream<8, 4, XMODE> (tests/test_conv3x3_wide_gpu.py).
 // Covered, row ranges: conv3x3_wide_plan.h.  profiles/conv3x3_wide_resources_v1.txt has the build's register, LDS and scratch figures.
 // MEASURED (profiles/conv3x3_wide_clip_breakdown_{parent,this}.txt, 294 400 pixels, NCHW): see DESIGN.md, "The FPN 3 x 3 convolution
 // with all 256 features per read of x"; profiles/conv3x3_wide_ablation_v1.txt has the kernel without its split / matrix instructions.
@@ -26,6 +26,7 @@
 #include "config.h"
 #include "conv3x3_wide_plan.h"
 #include "f16x3_kstep.h"
+#include "f16x3_wstream.h"
 #include "launchers.h"
 
 namespace univs {
@@ -37,15 +38,6 @@ struct CwArgs {
   float* Y;                      // [T, 256, H, W]
   int M, Cin, H, Wd, HW, rounds; // rounds: of every workgroup but the last (plan_conv3x3_wide)
 };
-
-// one wave's 1-KB piece: lane l's 16 bytes at `base` + `voff` -> LDS byte address `lds_dst` + 16 l (`base`, `lds_dst` wave-uniform).  M0
-// carries the destination and is written in the statement that uses it (linear_pair_xres.hip: px_glds16)
-__device__ __forceinline__ void cw_glds16(const u32x4* base, unsigned voff, unsigned lds_dst) {
-  unsigned keep;
-  const unsigned dst = __builtin_amdgcn_readfirstlane(lds_dst);
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-}
 
 template <int XMODE>
 __global__ __launch_bounds__(CW_THREADS) void conv3x3_wide(const CwArgs a) {
@@ -77,7 +69,7 @@ __global__ __launch_bounds__(CW_THREADS) void conv3x3_wide(const CwArgs a) {
     const u32x4* base = a.Wp + (size_t)s * IMG;
     const unsigned dst = lds_base + (unsigned)((img * IMG + 64 * wave) * 16);
 #pragma unroll
-    for (int v = 0; v < UPT; ++v) cw_glds16(base + CW_THREADS * v, w_voff, dst + (unsigned)(CW_THREADS * v * 16));
+    for (int v = 0; v < UPT; ++v) l3_glds16(base + CW_THREADS * v, w_voff, dst + (unsigned)(CW_THREADS * v * 16));
   };
 #pragma unroll
   for (int s = 0; s < 2; ++s) w_request(s, s);                   // the first pair of k-steps
@@ -127,14 +119,7 @@ __global__ __launch_bounds__(CW_THREADS) void conv3x3_wide(const CwArgs a) {
   typedef u32x4 Batch[2][2];                                     // [block of the batch][part h, m]
   auto read_batch = [](Batch& d, unsigned base, auto bc) __attribute__((always_inline)) {
     constexpr int b = decltype(bc)::value;
-    u32x4& d00 = d[0][0];                                        // (operands of an asm statement do not capture: name them first)
-    u32x4& d01 = d[0][1];
-    u32x4& d10 = d[1][0];
-    u32x4& d11 = d[1][1];
-    asm volatile("ds_read_b128 %0, %4 offset:%5\n\tds_read_b128 %1, %4 offset:%6\n\tds_read_b128 %2, %4 offset:%7\n\tds_read_b128 %3, %4 offset:%8"
-                 : "=&v"(d00), "=&v"(d01), "=&v"(d10), "=&v"(d11)
-                 : "v"(base), "n"(b * 512), "n"(b * 512 + CW_COUT * 16), "n"(b * 512 + 256), "n"(b * 512 + 256 + CW_COUT * 16)
-                 : "memory");
+    l3_read4<b * 512, b * 512 + CW_COUT * 16, b * 512 + 256, b * 512 + 256 + CW_COUT * 16>(d, base);
   };
   const unsigned a_lane = (unsigned)((g * 2 * CW_COUT + j) * 16);
 
@@ -202,18 +187,8 @@ __global__ __launch_bounds__(CW_THREADS) void conv3x3_wide(const CwArgs a) {
           if constexpr (b + 1 < NB) read_batch(afr[(b + 1) & 1], a_buf, std::integral_constant<int, b + 1>{});
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-          for (int qb = 0; qb < 2; ++qb) {
-            constexpr int rb0 = 2 * b;
-            const f16x8 ah = __builtin_bit_cast(f16x8, afr[b & 1][qb][0]);
-            const f16x8 am = __builtin_bit_cast(f16x8, afr[b & 1][qb][1]);
-            // smallest terms first: m*h', h*m', h*h' (l3_mfma_batch)
-            acc[rb0 + qb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am, bh[0], acc[rb0 + qb][0], 0, 0, 0);
-            acc[rb0 + qb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am, bh[1], acc[rb0 + qb][1], 0, 0, 0);
-            acc[rb0 + qb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bm[0], acc[rb0 + qb][0], 0, 0, 0);
-            acc[rb0 + qb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bm[1], acc[rb0 + qb][1], 0, 0, 0);
-            acc[rb0 + qb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[0], acc[rb0 + qb][0], 0, 0, 0);
-            acc[rb0 + qb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[1], acc[rb0 + qb][1], 0, 0, 0);
-          }
+          for (int qb = 0; qb < 2; ++qb)                         // one feature block after the other, as l3_mfma_batch
+            l3_mfma3_block<2>(__builtin_bit_cast(f16x8, afr[b & 1][qb][0]), __builtin_bit_cast(f16x8, afr[b & 1][qb][1]), bh, bm, acc[2 * b + qb]);
           __builtin_amdgcn_sched_barrier(0);
         });
       });
@@ -248,7 +223,7 @@ __global__ __launch_bounds__(CW_THREADS) void conv3x3_wide(const CwArgs a) {
 
 int conv3x3_wide_f32(int xmode, const float* x, const void* wp, const float* winv, float* y, int T, int Cin, int Cout, int H, int W,
                      hipStream_t st) {
-  if (config().linear_ablate == CW_ABLATE_OFF || T <= 0 || H <= 0 || W <= 0) return 0;
+  if (config().linear_ablate == LA_NO_CONV_WIDE || T <= 0 || H <= 0 || W <= 0) return 0;
   const long long M = (long long)T * H * W;
   if (!conv3x3_wide_covered(M, Cin, Cout) || !aligned16(x, wp, y, winv)) return 0;
   const WidePlan p = plan_conv3x3_wide(M, cu_count());

@@ -11,7 +11,6 @@ constexpr int CW_THREADS = 512;    // 8 waves, two per SIMD: one workgroup per C
 constexpr int CW_TILE_M = 32;      // pixels of a wave tile (two 16-column MFMA tiles), as GS_TILE_M
 constexpr int CW_COUT = 256;       // output features of the one instantiation: 16 MFMA feature blocks per wave
 constexpr int CW_IMAGES = 4;       // k-step images of W in LDS: the current pair of k-steps and the pair being requested
-constexpr int CW_ABLATE_OFF = 12;  // UnivsConfig.linear_ablate: the launchers keep gemm_f16x3_stream (A / B)
 
 // a k-step's image: [4 k-groups][2 parts][256 features] 16-byte units = the contiguous 32 KB of the pre-split image of presplit_f16x3
 constexpr size_t CW_IMAGE_BYTES = (size_t)4 * 2 * CW_COUT * 16;

@@ -1,6 +1,7 @@
-// The fp16 two-part split, row scales, GELU and instrumentation macros of the three-product kernels: included by f16x3_kstep.h (the k-step
-// of linear_f16x3.hip, linear_pair_f16x3.hip, gemm_f16x3_stream.hip), gemm_f16x3_tile.hip, mlp_f16x3.hip, small_linear.hip
-// and the attention cores (cross_attn.hip, window_attn_f16.hip).
+// The arithmetic contract of the three-product kernels, once: the fp16 two-part split, the row-scale rules and their numbers, the product
+// order (l3_mfma3_block / l3_mfma3_pair), GELU and the instrumentation macros.  Included by f16x3_kstep.h (the k-step of the W-in-LDS pass
+// kernels) and f16x3_wstream.h (the LDS-DMA weight stream of the operand-resident kernels), gemm_f16x3_tile.hip, small_linear.hip and the
+// attention cores (cross_attn.hip, window_attn_f16.hip: the split only).
 #pragma once
 #include "common.h"
 
@@ -12,14 +13,33 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
+// the numbers of the row-scale rules: the running scale's set point, the margin before it is lowered, the clamp of a row maximum's
+// exponent and of the exponent of an accumulator ratio
+constexpr int L3_SCALE_SET = 12, L3_SCALE_MARGIN = 2, L3_EXP_MIN = -100, L3_EXP_MAX = 128, L3_RATIO_MIN = -126;
+
 // power of two that brings a row whose largest magnitude has the bit pattern `maxbits` into [2^t, 2^(t+1)), and its inverse.
 // Zero rows and rows below 2^-100 keep a finite scale (2^(t+100)); an infinite maximum gives 2^(t-128).
 __device__ __forceinline__ void l3_scale(unsigned maxbits, int t, float& s, float& inv) {
   int e = (int)((maxbits >> 23) & 255u) - 127;            // 2^e <= max < 2^(e+1)
-  e = max(-100, min(e, 128));
+  e = max(L3_EXP_MIN, min(e, L3_EXP_MAX));
   s = __builtin_bit_cast(float, (unsigned)(127 + t - e) << 23);
   inv = __builtin_bit_cast(float, (unsigned)(127 - t + e) << 23);
 }
+
+// The RUNNING row scale's rule (f16x3_kstep.h has the state and the two-row step; gemm_f16x3_tile.hip, linear_pair_xres.hip and
+// mlp_f16x3.hip keep their own state): a row's scale is set for exponent `eset` -- values up to 2^(eset + 1) land below
+// 2^(L3_SCALE_SET + 1) --, is stale once a k-step's maximum has an exponent more than L3_SCALE_MARGIN above it, and is then set anew for
+// that exponent, the row's accumulators multiplied by the exact ratio 2^(old - new) <= 1.  The numbers exist here only.
+__device__ __forceinline__ int l3_scale_exp(unsigned maxbits) {              // 2^e <= max < 2^(e+1), clamped
+  return max(L3_EXP_MIN, min((int)((maxbits >> 23) & 255u) - 127, L3_EXP_MAX));
+}
+__device__ __forceinline__ bool l3_scale_stale(int enew, int eset) { return enew > eset + L3_SCALE_MARGIN; }
+__device__ __forceinline__ unsigned l3_scale_ratio_exp(int eold, int enew) {  // biased exponent of the ratio
+  return (unsigned)(127 + max(eold - enew, L3_RATIO_MIN));
+}
+__device__ __forceinline__ float l3_scale_ratio(int eold, int enew) { return __builtin_bit_cast(float, l3_scale_ratio_exp(eold, enew) << 23); }
+__device__ __forceinline__ float l3_scale_of(int e) { return __builtin_bit_cast(float, (unsigned)(127 + L3_SCALE_SET - e) << 23); }
+__device__ __forceinline__ float l3_scale_inv_of(int e) { return __builtin_bit_cast(float, (unsigned)(127 - L3_SCALE_SET + e) << 23); }
 
 // Timing experiments only (instrumented builds, `python -m univs_amd.build --ablate nosplit|nomfma|nosplit_nomfma`; results WRONG):
 //   UNIVS_ABLATE_NOSPLIT -- the x operand is taken as if it arrived pre-split (its 32 bytes per lane reinterpreted as the two fp16x8
@@ -32,6 +52,42 @@ __device__ __forceinline__ f32x4 l3_fake_mfma(f16x8 a, f16x8 b, f32x4 c) {
 }
 #define __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, x, y, z) l3_fake_mfma(a, b, c)
 #endif
+
+// THE PRODUCT ORDER of the family, and the only place its matrix instruction is spelled out (mlp_f16x3_ps issues the same order through
+// its ML_PS_MMA): per k-step of 32 the three products smallest terms first -- m h', h m', h h' -- where (h, m) are the parts of W and
+// (h', m') those of the operand, each product over all CT column tiles before the next.
+// One feature block (parts ah, am) on CT column tiles: acc[ct] += W_block x_ct^T
+template <int CT>
+__device__ __forceinline__ void l3_mfma3_block(f16x8 ah, f16x8 am, const f16x8 (&bh)[CT], const f16x8 (&bm)[CT], f32x4 (&acc)[CT]) {
+#pragma unroll
+  for (int ct = 0; ct < CT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am, bh[ct], acc[ct], 0, 0, 0);
+#pragma unroll
+  for (int ct = 0; ct < CT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bm[ct], acc[ct], 0, 0, 0);
+#pragma unroll
+  for (int ct = 0; ct < CT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[ct], acc[ct], 0, 0, 0);
+}
+// Two feature blocks (fragments fr[block][part h, m]) alternating, so that dependent accumulators are two issues apart
+template <int CT>
+__device__ __forceinline__ void l3_mfma3_pair(const u32x4 (&fr)[2][2], const f16x8 (&bh)[CT], const f16x8 (&bm)[CT], f32x4 (&c0)[CT],
+                                              f32x4 (&c1)[CT]) {
+  const f16x8 ah0 = __builtin_bit_cast(f16x8, fr[0][0]), am0 = __builtin_bit_cast(f16x8, fr[0][1]);
+  const f16x8 ah1 = __builtin_bit_cast(f16x8, fr[1][0]), am1 = __builtin_bit_cast(f16x8, fr[1][1]);
+#pragma unroll
+  for (int ct = 0; ct < CT; ++ct) {
+    c0[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am0, bh[ct], c0[ct], 0, 0, 0);
+    c1[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am1, bh[ct], c1[ct], 0, 0, 0);
+  }
+#pragma unroll
+  for (int ct = 0; ct < CT; ++ct) {
+    c0[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, bm[ct], c0[ct], 0, 0, 0);
+    c1[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, bm[ct], c1[ct], 0, 0, 0);
+  }
+#pragma unroll
+  for (int ct = 0; ct < CT; ++ct) {
+    c0[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, bh[ct], c0[ct], 0, 0, 0);
+    c1[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, bh[ct], c1[ct], 0, 0, 0);
+  }
+}
 
 // UNIVS_TRACE_GEMM (instrumented build `--ablate trace`): s_memtime stamps of a few (workgroup, wave) pairs at the phase boundaries of
 // linear_f16x3 / gemm_f16x3_stream, read back through univs_debug_gemm_trace_{linear,stream} (tools/gemm_trace.py).

@@ -1,9 +1,11 @@
 // One k-step of the three-product fp16 GEMM (f16x3.h; linear_f16x3.hip has the arithmetic) on a W image in LDS, for the kernels whose
 // waves hold 16 RB features x 32 rows: linear_f16x3.hip and linear_pair_f16x3.hip (W resident) and gemm_f16x3_stream.hip (W streamed).
-// These pieces ARE the family's arithmetic contract -- k order, scale rule, split, product order -- and exist once:
+// The arithmetic contract -- split, scale rule and its numbers, product order -- lives in f16x3.h; this header applies it to those kernels'
+// k-step, once:
 //   * the A-fragment pipeline: W parts from LDS in batches, read one batch ahead of the matrix instructions that use them;
-//   * the running row scale of one ring stage of x;
-//   * the three products of one batch.
+//   * the running row scale (l3_scale_* of f16x3.h) of one ring stage of x: two rows per lane;
+//   * the three products (l3_mfma3_block) of one batch.
+// conv3x3_wide.hip uses the same k-step on a W image that f16x3_wstream.h streams in.
 // What differs between the kernels stays in them: the order in which x is refilled, W fetched and committed and the next batch read.
 #pragma once
 #include "f16x3.h"
@@ -72,10 +74,10 @@ __device__ __forceinline__ void l3_wait_batch(u32x4 (&d)[BSZ][2]) {
 //     int enew[2];
 //     if (__builtin_amdgcn_ballot_w64(l3_row_scale_need(raw, eset, enew)) != 0) l3_row_scale_lower(enew, acc, eset, sx, sx_inv);   // rare
 // (as one function, or with the state in one struct, every kernel compiles into longer code: DESIGN.md, "One k-step core").
-// A new row tile: the first k-step sets the scale.  `frozen`: linear_f16x3's timing switch `ablate == 1` -- the scale stays at 1, and
+// A new row tile: the first k-step sets the scale.  `frozen`: linear_f16x3's timing switch LA_SCALE_FROZEN -- the scale stays at 1, and
 // the kernel skips the lowering.
 __device__ __forceinline__ void l3_row_scale_reset(int (&eset)[2], float (&sx)[2], float (&sx_inv)[2], bool frozen = false) {
-  eset[0] = eset[1] = frozen ? 12 : -1000;
+  eset[0] = eset[1] = frozen ? L3_SCALE_SET : -1000;
   sx[0] = sx[1] = sx_inv[0] = sx_inv[1] = 1.0f;
 }
 
@@ -86,8 +88,8 @@ __device__ __forceinline__ bool l3_row_scale_need(const f32x4 (&raw)[2][2], cons
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
     const unsigned mk = l3_row_max(l3_absmax8(raw[c][0], raw[c][1]));
-    enew[c] = max(-100, min((int)((mk >> 23) & 255u) - 127, 128));      // 2^e <= max < 2^(e+1)
-    need = need || (enew[c] > eset[c] + 2);
+    enew[c] = l3_scale_exp(mk);
+    need = need || l3_scale_stale(enew[c], eset[c]);
   }
   return need;
 }
@@ -99,18 +101,17 @@ __device__ __forceinline__ void l3_row_scale_lower(const int (&enew)[2], f32x4 (
                                                    float (&sx_inv)[2]) {
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
-    const bool mine = enew[c] > eset[c] + 2;
-    const int en = mine ? enew[c] : eset[c];
-    const float ratio = __builtin_bit_cast(float, (unsigned)(127 + max(eset[c] - en, -126)) << 23);   // 2^(old - new) <= 1
+    const int en = l3_scale_stale(enew[c], eset[c]) ? enew[c] : eset[c];
+    const float ratio = l3_scale_ratio(eset[c], en);
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) acc[rb][c] *= ratio;
     eset[c] = en;
-    sx[c] = __builtin_bit_cast(float, (unsigned)(127 + 12 - en) << 23);
-    sx_inv[c] = __builtin_bit_cast(float, (unsigned)(127 - 12 + en) << 23);
+    sx[c] = l3_scale_of(en);
+    sx_inv[c] = l3_scale_inv_of(en);
   }
 }
 
-// the three products of batch B on the split stage (bh, bm) of x: six MFMAs per feature block, the two column tiles interleaved
+// the three products of batch B on the split stage (bh, bm) of x: six MFMAs per feature block, in f16x3.h's order
 template <int RB, int B>
 __device__ __forceinline__ void l3_mfma_batch(const typename KStep<RB>::Batch& a, const f16x8 (&bh)[2], const f16x8 (&bm)[2],
                                               f32x4 (&acc)[RB][2]) {
@@ -118,17 +119,7 @@ __device__ __forceinline__ void l3_mfma_batch(const typename KStep<RB>::Batch& a
 #pragma unroll
   for (int q = 0; q < BSZ; ++q) {
     const int rb = B * BSZ + q;
-    if (rb < RB) {
-      const f16x8 ah = __builtin_bit_cast(f16x8, a[q][0]);
-      const f16x8 am = __builtin_bit_cast(f16x8, a[q][1]);
-      // smallest terms first: m*h', h*m', h*h'
-      acc[rb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am, bh[0], acc[rb][0], 0, 0, 0);
-      acc[rb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am, bh[1], acc[rb][1], 0, 0, 0);
-      acc[rb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bm[0], acc[rb][0], 0, 0, 0);
-      acc[rb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bm[1], acc[rb][1], 0, 0, 0);
-      acc[rb][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[0], acc[rb][0], 0, 0, 0);
-      acc[rb][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[1], acc[rb][1], 0, 0, 0);
-    }
+    if (rb < RB) l3_mfma3_block<2>(__builtin_bit_cast(f16x8, a[q][0]), __builtin_bit_cast(f16x8, a[q][1]), bh, bm, acc[rb]);
   }
 }
 

@@ -80,7 +80,7 @@ struct GsArgs {
   int M, N, K, rows_per_pass, epi;
   int Cin, Cout, H, Wd, HW;      // conv (XMODE 1): X [T, Cin, H, W], Y [T, Cout, H, W]; XMODE 2: X [T, H, W, Cin] (channels last), Y as XMODE 1
   int tap0;                      // conv: first tap of the kernel (0: all nine taps of a 3 x 3; 4: the centre alone = a 1 x 1)
-  int remap;                     // XCD-aware (row range, pass) order (UnivsConfig.linear_ablate == 5 switches it off: A/B)
+  int remap;                     // XCD-aware (row range, pass) order (UnivsConfig.linear_ablate == LA_NO_XCD_REMAP switches it off: A/B)
   const float* affine;           // AFF (a 1 x 1 on XMODE 1 / 2): (scale, bias) of every (frame, input channel) plane, [T * Cin][2]
 };
 
@@ -309,14 +309,14 @@ __global__ __launch_bounds__(GS_THREADS, 512 / GS_THREADS) void gemm_f16x3_strea
         if (__builtin_amdgcn_ballot_w64(l3_row_scale_need(raw[u], eset, enew)) != 0) {
 #pragma unroll
           for (int c = 0; c < 2; ++c) {
-            const bool mine = enew[c] > eset[c] + 2;
+            const bool mine = enew[c] > eset[c] + L3_SCALE_MARGIN;
             const int en = mine ? enew[c] : eset[c];
-            const float ratio = __builtin_bit_cast(float, (unsigned)(127 + max(eset[c] - en, -126)) << 23);
+            const float ratio = __builtin_bit_cast(float, (unsigned)(127 + max(eset[c] - en, L3_RATIO_MIN)) << 23);
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb) acc[rb][c] *= ratio;
             eset[c] = en;
-            sx[c] = __builtin_bit_cast(float, (unsigned)(127 + 12 - en) << 23);
-            sx_inv[c] = __builtin_bit_cast(float, (unsigned)(127 - 12 + en) << 23);
+            sx[c] = __builtin_bit_cast(float, (unsigned)(127 + L3_SCALE_SET - en) << 23);
+            sx_inv[c] = __builtin_bit_cast(float, (unsigned)(127 - L3_SCALE_SET + en) << 23);
           }
         }
         float s0 = sx[0], s1 = sx[1];
@@ -479,7 +479,7 @@ static int gs_conv(const float* x, const void* wp, const float* winv, const floa
 
 int conv3x3_f16x3_f32(const float* x, const void* wp, const float* winv, float* y, int T, int Cin, int Cout, int H, int W,
                       hipStream_t st) {
-  // all 256 output features on one read of x where that kernel covers the call (conv3x3_wide.hip; UnivsConfig.linear_ablate == 12
+  // all 256 output features on one read of x where that kernel covers the call (conv3x3_wide.hip; UnivsConfig.linear_ablate == LA_NO_CONV_WIDE
   // switches it off: A / B), else the passes of 128 features; the same bits either way
   if (const int rc = conv3x3_wide_f32(1, x, wp, winv, y, T, Cin, Cout, H, W, st); rc != 0) return rc == 1 ? UNIVS_OK : rc;
   return gs_conv<1>(x, wp, winv, nullptr, y, T, Cin, Cout, H, W, 9, st);

@@ -127,10 +127,10 @@ __global__ __launch_bounds__(GT_THREADS, OCC) void gemm_f16x3_tile(const GtArgs 
 #pragma unroll
     for (int sl = 0; sl < SLOTS; ++sl) {
       const unsigned mk = l3_row_max(l3_absmax8(xq[slot][sl][0], xq[slot][sl][1]));
-      const int enew = max(-100, min((int)((mk >> 23) & 255u) - 127, 128));      // 2^e <= max < 2^(e+1)
-      if (enew > eset[sl] + 2) {
+      const int enew = l3_scale_exp(mk);
+      if (l3_scale_stale(enew, eset[sl])) {
         eset[sl] = enew;
-        sx[sl] = __builtin_bit_cast(float, (unsigned)(127 + 12 - enew) << 23);
+        sx[sl] = l3_scale_of(enew);
       }
       f16x8 bh, bm;
       l3_split8(xq[slot][sl][0], xq[slot][sl][1], sx[sl], bh, bm);
@@ -168,24 +168,22 @@ __global__ __launch_bounds__(GT_THREADS, OCC) void gemm_f16x3_tile(const GtArgs 
     if (__builtin_amdgcn_ballot_w64(chg) != 0) {                 // rare after the first k-step
 #pragma unroll
       for (int c = 0; c < CT; ++c) {
-        const float ratio = __builtin_bit_cast(float, (unsigned)(127 + max(eprev[c] - e[c], -126)) << 23);   // 2^(old - new) <= 1
+        const float ratio = l3_scale_ratio(eprev[c], e[c]);
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) acc[rb][c] *= ratio;
         eprev[c] = e[c];
       }
     }
+    f16x8 bh[CT], bm[CT];
 #pragma unroll
-    for (int rb = 0; rb < RB; ++rb) {
-      const f16x8 ah = __builtin_bit_cast(f16x8, Ws[st * WS + a_unit + rb * 16]);
-      const f16x8 am = __builtin_bit_cast(f16x8, Ws[st * WS + a_unit + rb * 16 + TFp]);
-      // smallest terms first: m*h', h*m', h*h'
-#pragma unroll
-      for (int c = 0; c < CT; ++c) acc[rb][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am, __builtin_bit_cast(f16x8, bfr[c][0]), acc[rb][c], 0, 0, 0);
-#pragma unroll
-      for (int c = 0; c < CT; ++c) acc[rb][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, __builtin_bit_cast(f16x8, bfr[c][1]), acc[rb][c], 0, 0, 0);
-#pragma unroll
-      for (int c = 0; c < CT; ++c) acc[rb][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, __builtin_bit_cast(f16x8, bfr[c][0]), acc[rb][c], 0, 0, 0);
+    for (int c = 0; c < CT; ++c) {
+      bh[c] = __builtin_bit_cast(f16x8, bfr[c][0]);
+      bm[c] = __builtin_bit_cast(f16x8, bfr[c][1]);
     }
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb)
+      l3_mfma3_block<CT>(__builtin_bit_cast(f16x8, Ws[st * WS + a_unit + rb * 16]), __builtin_bit_cast(f16x8, Ws[st * WS + a_unit + rb * 16 + TFp]),
+                         bh, bm, acc[rb]);
   };
 
   // ---- pipeline: slot s mod NSLOT holds k-step s; at k-step s the loads of k-step s + NSLOT are requested into the slot the
@@ -212,7 +210,7 @@ __global__ __launch_bounds__(GT_THREADS, OCC) void gemm_f16x3_tile(const GtArgs 
   for (int c = 0; c < CT; ++c) {
     const int m = row0 + (wr * CT + c) * 16 + j;
     const bool row_ok = m < M;
-    const float sx_inv = __builtin_bit_cast(float, (unsigned)(127 - 12 + eprev[c]) << 23);
+    const float sx_inv = l3_scale_inv_of(eprev[c]);
     auto out_off = [&](int rb) __attribute__((always_inline)) -> unsigned {
       const int f = (wf * RB + rb) * 16 + 4 * g;
       return (row_ok && f < R) ? ((unsigned)m * (unsigned)N + (unsigned)(n0 + f)) * 4u : 0xFFFFFFF0u;   // out of range: dropped / 0

@@ -27,6 +27,18 @@ constexpr int L3_WPT = 24;        // PRE: 16-byte units of the W slab per thread
 constexpr int GS_THREADS = UNIVS_GS_THREADS;
 constexpr int GS_TILE_M = 32;
 constexpr int GT_THREADS = 512;
+// UnivsConfig.linear_ablate: the family's timing experiments and A / B switches (include/univs_hip.h describes each value)
+enum LinearAblate {
+  LA_NONE = 0,
+  LA_SCALE_FROZEN = 1,                                            // linear_f16x3: no running row scale
+  LA_MLP_NOMFMA = 2, LA_MLP_NOREADS = 3, LA_MLP_NOACT = 4,        // mlp_f16x3<.., ABL = value - 1, ..>: results WRONG
+  LA_NO_XCD_REMAP = 5,                                            // linear_f16x3 / gemm_f16x3_stream in plain block order
+  LA_NO_TILE = 6,                                                 // univs_linear_presplit_f32 keeps gemm_f16x3_stream
+  LA_TILE_NSLOT2 = 7, LA_TILE_NSLOT3 = 8, LA_TILE_NSLOT4 = 9,     // gemm_f16x3_tile with value - 5 k-steps of loads in flight
+  LA_MLP_PHASE_SHIFT = 10,                                        // mlp_f16x3_ps
+  LA_NO_PAIR_XRES = 11,                                           // the encoder pair entry keeps linear_pair_f16x3
+  LA_NO_CONV_WIDE = 12,                                           // the 3 x 3 convolutions keep gemm_f16x3_stream
+};
 enum { EPI_NONE = 0, EPI_RELU = 1, EPI_GELU = 2, EPI_RESIDUAL = 3, EPI_BLOCKED = 4 };   // the kernels' LS_ / L3_ / GS_ / GT_EPI_* alias these
 
 // ---- coverage predicates
@@ -217,7 +229,7 @@ inline StreamPlan plan_stream(int xmode, long long M, int N, int K, int n_cu, co
   p.gx = (unsigned)gx;
   p.passes = (unsigned)pp.passes;
   p.rows_per_pass = pp.rows;
-  p.remap = cfg.linear_ablate == 5 ? 0 : 1;                // XCD-aware (row range, pass) order; 5 switches it off: A / B
+  p.remap = cfg.linear_ablate == LA_NO_XCD_REMAP ? 0 : 1;  // XCD-aware (row range, pass) order
   return p;
 }
 
@@ -236,7 +248,8 @@ inline TilePlan plan_tile(long long M, int N, int K, int n_cu, const UnivsConfig
   // k-steps in flight per workgroup (register slots of the loads): 4 where K allows -- with 2 a k-step took ~5 000 clocks at
   // 18 400 x 1536 -> 384, one memory latency under load: 44 KB in flight per CU, against the ~100 KB the L2 -> CU stream needs
   int nslot = K % 128 == 0 ? 4 : K % 96 == 0 ? 3 : 2;
-  if (cfg.linear_ablate >= 7 && cfg.linear_ablate <= 9 && K % (32 * (cfg.linear_ablate - 5)) == 0) nslot = cfg.linear_ablate - 5;   // kernel benchmarks
+  if (cfg.linear_ablate >= LA_TILE_NSLOT2 && cfg.linear_ablate <= LA_TILE_NSLOT4 && K % (32 * (cfg.linear_ablate - 5)) == 0)
+    nslot = cfg.linear_ablate - 5;                                // kernel benchmarks
   // tile shape: the (CT, RB) with the least estimated time.  Per k-step and workgroup: the matrix pipe (two waves per SIMD), the LDS port
   // (fragment reads of the 8 waves + the stage writes, 128 B / clock) and the L2 -> CU stream (~14 B / clock and CU measured for this
   // access pattern: tools/probes/row_stride.hip).  One workgroup per CU: vector / memory phase and matrix phase add up (measured:

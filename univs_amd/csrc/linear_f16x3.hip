@@ -60,7 +60,7 @@ __global__ __launch_bounds__(L3_THREADS, 1) void linear_f16x3(const float* __res
   // chunk of the sequence (row range major, pass minor): the passes of a row range -- which stream the same rows of x -- run on ONE XCD
   // and meet in its L2, whatever the grid extents (with 12 passes over 21 row ranges every XCD used to fetch nearly all of x itself).
   unsigned bx = blockIdx.x, by = blockIdx.y;
-  if (ablate != 5 && gridDim.y > 1) {
+  if (ablate != LA_NO_XCD_REMAP && gridDim.y > 1) {
     const unsigned lw = xcd_remap(blockIdx.x + gridDim.x * blockIdx.y, gridDim.x * gridDim.y);
     bx = lw / gridDim.y;
     by = lw - bx * gridDim.y;
@@ -251,7 +251,7 @@ __global__ __launch_bounds__(L3_THREADS, 1) void linear_f16x3(const float* __res
     for (int u = 0; u < RING; ++u) {
       const int ks = ks0 + u;
       int enew[2];                                                // the running row scale
-      if (__builtin_amdgcn_ballot_w64(l3_row_scale_need(raw[u], eset, enew)) != 0 && ablate != 1) l3_row_scale_lower(enew, acc, eset, sx, sx_inv);   // rare
+      if (__builtin_amdgcn_ballot_w64(l3_row_scale_need(raw[u], eset, enew)) != 0 && ablate != LA_SCALE_FROZEN) l3_row_scale_lower(enew, acc, eset, sx, sx_inv);   // rare
       float s0 = sx[0], s1 = sx[1];
       asm volatile("" : "+v"(s0), "+v"(s1) : : "memory");      // pins the consumption of ring stage u here
       f16x8 bh[2], bm[2];
@@ -282,7 +282,7 @@ __global__ __launch_bounds__(L3_THREADS, 1) void linear_f16x3(const float* __res
   for (int tile = 0; tile < ntiles; ++tile) {
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) acc[rb][0] = acc[rb][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    l3_row_scale_reset(eset, sx, sx_inv, ablate == 1);
+    l3_row_scale_reset(eset, sx, sx_inv, ablate == LA_SCALE_FROZEN);
 #pragma unroll 1
     for (int ks0 = 0; ks0 < KS; ks0 += RING) group(ks0, ks0 + RING >= KS);
     UNIVS_GT(g_l3_trace, gts, 3 + 2 * tile);

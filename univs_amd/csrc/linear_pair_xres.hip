@@ -13,21 +13,21 @@
 //     instructions per SIMD, less than a loaded L2's latency: with two images the barrier waited for the stream), one barrier per
 //     chunk: 8 chunks of A, 9 of B per row group;
 //   * a chunk's k loop replays the schedule: where the scale was lowered at k-step t, the chunk's accumulators are multiplied by the
-//     same exact power of two before the k-step's three products (smallest first, as l3_mfma_batch issues them).
+//     same exact power of two before the k-step's three products (l3_mfma3_pair: f16x3.h's order).
 // ARITHMETIC: a feature's sum depends on its row of W, its row of the operand and that row's sequence of scales only, and all three are
 // those of linear_f16x3<.., true> -- so each output has the bits of linear_pair_f16x3 and of univs_linear_blocked_presplit_f32 on the
 // materialised operand (tests/test_encoder_pair_xres_gpu.py).  The lowering is decided wave-wide by ballot there (32 rows) and here
 // (16 rows); a row that does not need it is multiplied by 2^0 and keeps its scale, so the vote's width does not enter the result.
 // STORES: a chunk's 32 features of 16 rows leave as two 16-byte stores per lane, issued in the NEXT chunk behind its DMA requests: the
 // counted wait for a chunk's pieces in front of its barrier then reaches back only to stores three chunks old (see the loop).
-// Fragments are requested two batches ahead with counted lgkmcnt waits, as in mlp_f16x3.hip.
+// Stream pieces, fragment reads (two batches ahead) and counted lgkmcnt waits are f16x3_wstream.h's; the schedule below is this kernel's.
 // Covered: pair_xres_plan.h.  profiles/encoder_xres_resources_v1.txt has the build's register, LDS and scratch figures.
 // MEASURED (profiles/encoder_xres_clip_breakdown_{parent,this}.txt, 96 600 rows): 120.7 us against the pass kernel's 148.5 on the same
 // box.  Its parts add rather than overlap (profiles/encoder_xres_ablation_v1.txt): stores 20 us, matrix instructions 28, LDS reads 19,
 // weight stream 12, and 56 us for what is left without them -- mostly the tile build, which nothing runs beside.
 #include "common.h"
 #include "config.h"
-#include "f16x3.h"
+#include "f16x3_wstream.h"
 #include "pair_xres_plan.h"
 
 namespace univs {
@@ -46,23 +46,6 @@ struct XresArgs {
   XresProblem p[2];
 };
 
-template <int N>
-__device__ __forceinline__ void px_wait_lgkm(u32x4 (&d)[2][2]) {   // the operands tie the MFMAs behind this wait
-  static_assert(N == 0 || N == 4, "the two counts of the fragment pipeline");
-  if constexpr (N == 0) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(d[0][0]), "+v"(d[0][1]), "+v"(d[1][0]), "+v"(d[1][1]) : : "memory");
-  else asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(d[0][0]), "+v"(d[0][1]), "+v"(d[1][0]), "+v"(d[1][1]) : : "memory");
-}
-
-// one wave's 1-KB piece: lane l's 16 bytes at `base` + `voff` -> LDS byte address `lds_dst` + 16 l (`base`, `lds_dst` wave-uniform; the
-// lane's part of the address is a 32-bit offset: no 64-bit vector arithmetic in the stream).  M0 carries the destination and is written
-// in the statement that uses it (mlp_f16x3.hip: ml_glds16)
-__device__ __forceinline__ void px_glds16(const u32x4* base, unsigned voff, unsigned lds_dst) {
-  unsigned keep;
-  const unsigned dst = __builtin_amdgcn_readfirstlane(lds_dst);
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-}
-
 // The running row scale of f16x3_kstep.h for ONE row per lane (l3_row_scale_need / l3_row_scale_lower hold two), with the accumulators'
 // rescaling recorded instead of applied: `sched` byte t = the biased exponent of the ratio 2^(old - new) of k-step t, `mask` bit t = some
 // row of the wave was lowered at k-step t (wave-uniform).
@@ -74,16 +57,16 @@ struct PxScale {
 template <int T>
 __device__ __forceinline__ void px_scale_step(const f32x4 v0, const f32x4 v1, PxScale& s) {
   const unsigned mk = l3_row_max(l3_absmax8(v0, v1));
-  const int enew = max(-100, min((int)((mk >> 23) & 255u) - 127, 128));      // 2^e <= max < 2^(e+1)
-  const bool mine = enew > s.eset + 2;
+  const int enew = l3_scale_exp(mk);
+  const bool mine = l3_scale_stale(enew, s.eset);
   if (__builtin_amdgcn_ballot_w64(mine) != 0) {                               // rare after the first k-step
     const int en = mine ? enew : s.eset;
-    const unsigned rexp = (unsigned)(127 + max(s.eset - en, -126));           // ratio 2^(old - new) <= 1
+    const unsigned rexp = l3_scale_ratio_exp(s.eset, en);                     // ratio 2^(old - new) <= 1
     s.sched[T >> 2] |= rexp << (8 * (T & 3));
     s.mask |= 1u << T;
     s.eset = en;
-    s.sx = __builtin_bit_cast(float, (unsigned)(127 + 12 - en) << 23);
-    s.sx_inv = __builtin_bit_cast(float, (unsigned)(127 - 12 + en) << 23);
+    s.sx = l3_scale_of(en);
+    s.sx_inv = l3_scale_inv_of(en);
   }
 }
 
@@ -125,7 +108,7 @@ __global__ __launch_bounds__(PX_THREADS) void linear_pair_xres(const XresArgs a)
   };
 #pragma unroll
   for (int v = 0; v < (PX_IMAGES - 1) * UPT; ++v)                // A's first chunks -> images 0 .. PX_IMAGES - 2 (N_a: host-checked)
-    px_glds16(w_base(a.p[0], v / UPT, v % UPT), w_voff(a.p[0]), lds_base + (unsigned)(((v / UPT) * CHU + PX_THREADS * (v % UPT) + 64 * wave) * 16));
+    l3_glds16(w_base(a.p[0], v / UPT, v % UPT), w_voff(a.p[0]), lds_base + (unsigned)(((v / UPT) * CHU + PX_THREADS * (v % UPT) + 64 * wave) * 16));
 
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.X), 0, (int)((long long)M * K * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.add), 0, (int)((long long)a.add_rows * K * 4), 0x00020000);
@@ -134,16 +117,9 @@ __global__ __launch_bounds__(PX_THREADS) void linear_pair_xres(const XresArgs a)
 
   u32x4 afr[3][2][2];                                            // [ring][block][part]
   // batch T = k-step T of a chunk image at lane address `addr`: the k-step, block and part offsets are immediates of the reads
-  auto read_batch = [&](u32x4 (&d)[2][2], unsigned addr, auto tc) __attribute__((always_inline)) {
+  auto read_batch = [](u32x4 (&d)[2][2], unsigned addr, auto tc) __attribute__((always_inline)) {
     constexpr int T = decltype(tc)::value;
-    u32x4& d00 = d[0][0];                                        // (operands of an asm statement do not capture: name them first)
-    u32x4& d01 = d[0][1];
-    u32x4& d10 = d[1][0];
-    u32x4& d11 = d[1][1];
-    asm volatile("ds_read_b128 %0, %4 offset:%5\n\tds_read_b128 %1, %4 offset:%6\n\tds_read_b128 %2, %4 offset:%7\n\tds_read_b128 %3, %4 offset:%8"
-                 : "=&v"(d00), "=&v"(d01), "=&v"(d10), "=&v"(d11)
-                 : "v"(addr), "n"(T * 4096), "n"(T * 4096 + 512), "n"(T * 4096 + 256), "n"(T * 4096 + 768)
-                 : "memory");
+    l3_read4<T * 4096, T * 4096 + 512, T * 4096 + 256, T * 4096 + 768>(d, addr);
   };
   // byte address inside a chunk image of (k-step t, block q, part): ((t 4 + g) 2 + part) 32 + 16 q + j units
   const unsigned a_lane = (unsigned)((g * 64 + j) * 16);
@@ -194,16 +170,16 @@ __global__ __launch_bounds__(PX_THREADS) void linear_pair_xres(const XresArgs a)
       const int ncx = wrap ? c + PX_IMAGES - 1 - NC : c + PX_IMAGES - 1;
       const unsigned nvoff = w_voff(np);
 
-      f32x4 acc[2];
-      acc[0] = acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      f32x4 acc[2][1];                                           // [block][the wave's one column tile]
+      acc[0][0] = acc[1][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
       // one batch slot = one k-step: this slot's piece of the weight stream, wait for batch T's fragments, request batch T + 2, the
       // schedule's rescaling, six MFMAs
       l3_static_for<0, KS>([&](auto tc) __attribute__((always_inline)) {
         constexpr int T = decltype(tc)::value;
         if constexpr (T == UPT) flush();                         // the stores of the chunk before: behind this chunk's pieces
-        if constexpr (T < UPT) px_glds16(w_base(np, ncx, T), nvoff, wdma + (unsigned)(PX_THREADS * T * 16));
+        if constexpr (T < UPT) l3_glds16(w_base(np, ncx, T), nvoff, wdma + (unsigned)(PX_THREADS * T * 16));
         __builtin_amdgcn_sched_barrier(0);
-        px_wait_lgkm<(T + 1 < KS ? 4 : 0)>(afr[T % 3]);          // (no LDS operation of mine behind the next batch's reads)
+        l3_wait_lgkm<(T + 1 < KS ? 4 : 0)>(afr[T % 3]);          // (no LDS operation of mine behind the next batch's reads)
         if constexpr (T + 2 < KS) read_batch(afr[(T + 2) % 3], a1, std::integral_constant<int, T + 2>{});
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (T > 0) {                                   // (k-step 0 sets the scale: the accumulators are still zero)
@@ -211,19 +187,12 @@ __global__ __launch_bounds__(PX_THREADS) void linear_pair_xres(const XresArgs a)
             unsigned w = sc.sched[T >> 2];
             asm volatile("" : "+v"(w));                          // (formed here: hoisted, the seven ratios cost 28 registers)
             const float ratio = __builtin_bit_cast(float, ((w >> (8 * (T & 3))) & 255u) << 23);
-            acc[0] *= ratio;
-            acc[1] *= ratio;
+            acc[0][0] *= ratio;
+            acc[1][0] *= ratio;
           }
         }
-        const f16x8 ah0 = __builtin_bit_cast(f16x8, afr[T % 3][0][0]), am0 = __builtin_bit_cast(f16x8, afr[T % 3][0][1]);
-        const f16x8 ah1 = __builtin_bit_cast(f16x8, afr[T % 3][1][0]), am1 = __builtin_bit_cast(f16x8, afr[T % 3][1][1]);
-        // smallest terms first: m h', h m', h h'; the two blocks alternate (dependent accumulators two issues apart)
-        acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am0, xh[T], acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am1, xh[T], acc[1], 0, 0, 0);
-        acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, xm[T], acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, xm[T], acc[1], 0, 0, 0);
-        acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, xh[T], acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, xh[T], acc[1], 0, 0, 0);
+        const f16x8 bh[1] = {xh[T]}, bm[1] = {xm[T]};
+        l3_mfma3_pair<1>(afr[T % 3], bh, bm, acc[0], acc[1]);
         __builtin_amdgcn_sched_barrier(0);
       });
 
@@ -233,7 +202,7 @@ __global__ __launch_bounds__(PX_THREADS) void linear_pair_xres(const XresArgs a)
         const int f = PX_CHUNK * c + 16 * q + 4 * g;
         const f32x4 wi = *reinterpret_cast<const f32x4*>(winv_lds + f);
         const f32x4 bi = *reinterpret_cast<const f32x4*>(bias_lds + f);
-        const f32x4 v = (acc[q] * sc.sx_inv) * wi + bi;          // two exact unscalings, then the bias
+        const f32x4 v = (acc[q][0] * sc.sx_inv) * wi + bi;          // two exact unscalings, then the bias
         const unsigned cb = (unsigned)f / blk_cols;
         const unsigned off = (rowpart + cb * blk_rows * blk_cols + ((unsigned)f - cb * blk_cols)) * 4u;
         pend[q] = __builtin_bit_cast(u32x4, v);
@@ -291,7 +260,7 @@ __global__ __launch_bounds__(PX_THREADS) void linear_pair_xres(const XresArgs a)
 int linear_pair_xres_f32(const float* x, const float* add, long long add_rows, const void* wp_a, const float* winv_a, const float* bias_a,
                          int N_a, int blk_cols_a, float* y_a, const void* wp_b, const float* winv_b, const float* bias_b, int N_b,
                          int blk_cols_b, float* y_b, long long M, int K, long long blk_rows, void* stream) {
-  if (config().linear_ablate == PX_ABLATE_OFF) return 0;
+  if (config().linear_ablate == LA_NO_PAIR_XRES) return 0;
   const int n_cu = cu_count();
   if (!pair_xres_covered(M, N_a, N_b, K, add_rows, blk_rows, blk_cols_a, blk_cols_b, n_cu) ||
       !aligned16(x, add, static_cast<const float*>(wp_a), winv_a, bias_a, y_a, static_cast<const float*>(wp_b), winv_b, bias_b, y_b))

@@ -21,9 +21,11 @@
 // ahead into a ring of three; the wait before a batch is `s_waitcnt lgkmcnt(n)` with n = the LDS operations issued after
 // that batch's reads (the next batch's four reads + this slot's commits): LDS operations complete in order and the loop
 // holds no scalar memory operation (checked in the ISA), so the count is exact.
+// The DMA piece, the batch read and the counted wait are f16x3_wstream.h's; product order and the scale rule's numbers f16x3.h's.
 #include "common.h"
 #include "config.h"
-#include "f16x3.h"
+#include "f16x3_wstream.h"
+#include "gemm_plan.h"
 #include "launchers.h"
 
 #include <algorithm>
@@ -33,7 +35,7 @@
 namespace univs {
 
 enum { ML_ACT_RELU = 1, ML_ACT_GELU = 2 };
-// ABL (timing experiments, UnivsConfig.linear_ablate = 2 / 3 / 4; results are then WRONG): 1 no MFMAs, 2 no LDS reads of the A
+// ABL (timing experiments, UnivsConfig.linear_ablate = LA_MLP_NOMFMA / _NOREADS / _NOACT; results are then WRONG): 1 no MFMAs, 2 no LDS reads of the A
 // fragments, 3 no activation / scale / split of the hidden activations
 
 struct MlpArgs {
@@ -73,28 +75,6 @@ __device__ __forceinline__ float ml_row_sum(float v) {
   return __uint_as_float(s2.x) + __uint_as_float(s2.y);
 }
 
-template <int N>
-__device__ __forceinline__ void ml_wait_lgkm(u32x4 (&d)[2][2]) {   // the operands tie the MFMAs behind this wait
-  static_assert(N >= 0 && N <= 15, "lgkmcnt is a 4-bit counter");
-  if constexpr (N == 0) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(d[0][0]), "+v"(d[0][1]), "+v"(d[1][0]), "+v"(d[1][1]) : : "memory");
-  else if constexpr (N == 1) asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(d[0][0]), "+v"(d[0][1]), "+v"(d[1][0]), "+v"(d[1][1]) : : "memory");
-  else if constexpr (N == 2) asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(d[0][0]), "+v"(d[0][1]), "+v"(d[1][0]), "+v"(d[1][1]) : : "memory");
-  else if constexpr (N == 3) asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(d[0][0]), "+v"(d[0][1]), "+v"(d[1][0]), "+v"(d[1][1]) : : "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(d[0][0]), "+v"(d[0][1]), "+v"(d[1][0]), "+v"(d[1][1]) : : "memory");
-  else if constexpr (N == 5) asm volatile("s_waitcnt lgkmcnt(5)" : "+v"(d[0][0]), "+v"(d[0][1]), "+v"(d[1][0]), "+v"(d[1][1]) : : "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(d[0][0]), "+v"(d[0][1]), "+v"(d[1][0]), "+v"(d[1][1]) : : "memory");
-  else if constexpr (N == 7) asm volatile("s_waitcnt lgkmcnt(7)" : "+v"(d[0][0]), "+v"(d[0][1]), "+v"(d[1][0]), "+v"(d[1][1]) : : "memory");
-  else asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(d[0][0]), "+v"(d[0][1]), "+v"(d[1][0]), "+v"(d[1][1]) : : "memory");
-}
-
-template <int I, int N, class F>
-__device__ __forceinline__ void ml_static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    ml_static_for<I + 1, N>(f);
-  }
-}
-
 // static schedule of the weight stream: unit v of a thread is fetched in batch slot ml_fs(v) and committed ML_D slots later
 constexpr int ml_dist(int nbat) { return nbat / 4 > 2 ? nbat / 4 : 2; }
 constexpr int ml_fs(int v, int upt, int nbat) { return v * (nbat - ml_dist(nbat)) / upt; }
@@ -115,14 +95,6 @@ constexpr bool ML_GLDS = false;
 #else
 constexpr bool ML_GLDS = true;
 #endif
-// one wave's 1-KB piece: lane l's 16 bytes at `gsrc` -> LDS byte address `lds_dst` + 16 l (`lds_dst` wave-uniform).  M0 carries the
-// destination and is written in the statement that uses it (the compiler does not preserve it around asm statements).
-__device__ __forceinline__ void ml_glds16(const u32x4* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  const unsigned dst = __builtin_amdgcn_readfirstlane(lds_dst);  // (an "s" operand the compiler holds in a vector register is passed as one)
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-}
 
 constexpr int ml_ring(int upt, int nbat) {          // most units in flight at once (after a slot's commits and fetches)
   int worst = 1;
@@ -220,12 +192,7 @@ __global__ __launch_bounds__(64 * NW, DB ? 2 : 1) void mlp_f16x3(const MlpArgs a
       for (int q = 0; q < 2; ++q) afr[r][q][0] = afr[r][q][1] = (u32x4){0x3c003c00u, 0x3c003c00u, 0x3c003c00u, 0x3c003c00u};
   }
   auto read_batch = [&](u32x4 (&d)[2][2], unsigned addr, unsigned pstride) __attribute__((always_inline)) {
-    if (ABL == 2) return;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const unsigned ah = addr + (unsigned)(q * 256);
-      asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3" : "=&v"(d[q][0]), "=&v"(d[q][1]) : "v"(ah), "v"(ah + pstride) : "memory");
-    }
+    if (ABL != 2) l3_read4(d, addr, pstride);
   };
   // byte addresses inside a chunk image: GEMM 1 (k-step t, block q): ((t*4 + g)*2 + part)*32 + 16 q + j units;
   // GEMM 2 (blocks 2 t + q): W1U + (g*2 + part)*C + 16 (2 t + q) + j units
@@ -327,27 +294,27 @@ __global__ __launch_bounds__(64 * NW, DB ? 2 : 1) void mlp_f16x3(const MlpArgs a
       auto slot = [&](auto tc) __attribute__((always_inline)) {
         constexpr int T = decltype(tc)::value;
         if constexpr (GLDS) {
-          ml_static_for<0, UPT>([&](auto vc) __attribute__((always_inline)) {
+          l3_static_for<0, UPT>([&](auto vc) __attribute__((always_inline)) {
             constexpr int V = decltype(vc)::value;
-            if constexpr (ml_dma_slot(V, UPT, NBAT) == T) ml_glds16(w_src(cn, V), wdma + (unsigned)(THREADS * V * 16));
+            if constexpr (ml_dma_slot(V, UPT, NBAT) == T) l3_glds16(w_src(cn, V), wdma + (unsigned)(THREADS * V * 16));
           });
           __builtin_amdgcn_sched_barrier(0);
-          if (ABL != 2) ml_wait_lgkm<(T + 1 < NBAT ? 4 : 0)>(afr[T % 3]);     // (no LDS operation of mine behind the next batch's reads)
+          if (ABL != 2) l3_wait_lgkm<(T + 1 < NBAT ? 4 : 0)>(afr[T % 3]);     // (no LDS operation of mine behind the next batch's reads)
           if constexpr (T + 2 < NBAT) {
             if constexpr (T + 2 < KS1) read_batch(afr[(T + 2) % 3], a1 + (unsigned)((T + 2) * 4096), 512u);
             else read_batch(afr[(T + 2) % 3], a2 + (unsigned)((T + 2 - KS1) * 512), (unsigned)(C * 16));
           }
         } else if constexpr (DB) {
-          ml_static_for<0, UPT>([&](auto vc) __attribute__((always_inline)) {
+          l3_static_for<0, UPT>([&](auto vc) __attribute__((always_inline)) {
             constexpr int V = decltype(vc)::value;
             if constexpr (ml_fs(V, UPT, NBAT) + WD == T) wdst[THREADS * V] = wreg[V % WR];
           });
-          ml_static_for<0, UPT>([&](auto vc) __attribute__((always_inline)) {
+          l3_static_for<0, UPT>([&](auto vc) __attribute__((always_inline)) {
             constexpr int V = decltype(vc)::value;
             if constexpr (ml_fs(V, UPT, NBAT) == T) wreg[V % WR] = *w_src(cn, V);
           });
           __builtin_amdgcn_sched_barrier(0);
-          if (ABL != 2) ml_wait_lgkm<(T + 1 < NBAT ? 4 : 0) + ml_commits_in(T, UPT, NBAT)>(afr[T % 3]);
+          if (ABL != 2) l3_wait_lgkm<(T + 1 < NBAT ? 4 : 0) + ml_commits_in(T, UPT, NBAT)>(afr[T % 3]);
           if constexpr (T + 2 < NBAT) {
             if constexpr (T + 2 < KS1) read_batch(afr[(T + 2) % 3], a1 + (unsigned)((T + 2) * 4096), 512u);
             else read_batch(afr[(T + 2) % 3], a2 + (unsigned)((T + 2 - KS1) * 512), (unsigned)(C * 16));
@@ -357,17 +324,17 @@ __global__ __launch_bounds__(64 * NW, DB ? 2 : 1) void mlp_f16x3(const MlpArgs a
           // W1 part of the NEXT chunk (units 0 ...); fragment requests do not cross the barrier between the two products
           constexpr int PT = T < KS1 ? T : T - KS1;                // slot within its phase
           constexpr int UOFF = T < KS1 ? UPH : 0;                  // first unit (per thread) of the part this phase refills
-          ml_static_for<0, UPH>([&](auto vc) __attribute__((always_inline)) {
+          l3_static_for<0, UPH>([&](auto vc) __attribute__((always_inline)) {
             constexpr int V = decltype(vc)::value;
             if constexpr (ml_fs(V, UPH, KS1) + WD == PT) wdst[THREADS * (UOFF + V)] = wreg[V % WR];
           });
-          ml_static_for<0, UPH>([&](auto vc) __attribute__((always_inline)) {
+          l3_static_for<0, UPH>([&](auto vc) __attribute__((always_inline)) {
             constexpr int V = decltype(vc)::value;
             if constexpr (ml_fs(V, UPH, KS1) == PT) wreg[V % WR] = *w_src(T < KS1 ? c : cn, UOFF + V);
           });
           __builtin_amdgcn_sched_barrier(0);
           constexpr bool next_requested = T < KS1 ? (T + 1 < KS1) : (T + 1 < NBAT);
-          if (ABL != 2) ml_wait_lgkm<(next_requested ? 4 : 0) + ml_commits_in(PT, UPH, KS1)>(afr[T % 3]);
+          if (ABL != 2) l3_wait_lgkm<(next_requested ? 4 : 0) + ml_commits_in(PT, UPH, KS1)>(afr[T % 3]);
           if constexpr (T < KS1) {
             if constexpr (T + 2 < KS1) read_batch(afr[(T + 2) % 3], a1 + (unsigned)((T + 2) * 4096), 512u);
           } else if constexpr (T + 2 < NBAT) {
@@ -376,48 +343,23 @@ __global__ __launch_bounds__(64 * NW, DB ? 2 : 1) void mlp_f16x3(const MlpArgs a
         }
         __builtin_amdgcn_sched_barrier(0);
         if (ABL != 1) {
-          const f16x8 ah0 = __builtin_bit_cast(f16x8, afr[T % 3][0][0]), am0 = __builtin_bit_cast(f16x8, afr[T % 3][0][1]);
-          const f16x8 ah1 = __builtin_bit_cast(f16x8, afr[T % 3][1][0]), am1 = __builtin_bit_cast(f16x8, afr[T % 3][1][1]);
-          // smallest terms first: m h', h m', h h'; the two blocks alternate (dependent accumulators two issues apart)
+          // the three products of the batch's two blocks on all CT column tiles (l3_mfma3_pair: f16x3.h's order)
           if constexpr (T < KS1) {                               // GEMM 1: acc1[block][ct] += W1[chunk rows] x^T, k-step T
+            f16x8 bh[CT], bm[CT];
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
-              acc1[0][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am0, xh[ct][T], acc1[0][ct], 0, 0, 0);
-              acc1[1][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am1, xh[ct][T], acc1[1][ct], 0, 0, 0);
+              bh[ct] = xh[ct][T];
+              bm[ct] = xm[ct][T];
             }
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-              acc1[0][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, xm[ct][T], acc1[0][ct], 0, 0, 0);
-              acc1[1][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, xm[ct][T], acc1[1][ct], 0, 0, 0);
-            }
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-              acc1[0][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, xh[ct][T], acc1[0][ct], 0, 0, 0);
-              acc1[1][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, xh[ct][T], acc1[1][ct], 0, 0, 0);
-            }
+            l3_mfma3_pair<CT>(afr[T % 3], bh, bm, acc1[0], acc1[1]);
           } else {                                               // GEMM 2: acc2[blocks 2 t, 2 t + 1][ct] += W2[rows][k-step c] h^T
-            constexpr int B0 = 2 * (T - KS1), B1 = B0 + 1;
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-              acc2[B0][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am0, hh[ct], acc2[B0][ct], 0, 0, 0);
-              acc2[B1][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am1, hh[ct], acc2[B1][ct], 0, 0, 0);
-            }
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-              acc2[B0][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, hm[ct], acc2[B0][ct], 0, 0, 0);
-              acc2[B1][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, hm[ct], acc2[B1][ct], 0, 0, 0);
-            }
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-              acc2[B0][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, hh[ct], acc2[B0][ct], 0, 0, 0);
-              acc2[B1][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, hh[ct], acc2[B1][ct], 0, 0, 0);
-            }
+            l3_mfma3_pair<CT>(afr[T % 3], hh, hm, acc2[2 * (T - KS1)], acc2[2 * (T - KS1) + 1]);
           }
         }
         __builtin_amdgcn_sched_barrier(0);
       };
 
-      ml_static_for<0, KS1>(slot);
+      l3_static_for<0, KS1>(slot);
       if constexpr (!DB) {
         __syncthreads();                                         // this chunk's W2 part is complete; everybody is done with the W1 part
         read_batch(afr[KS1 % 3], a2, (unsigned)(C * 16));
@@ -459,20 +401,21 @@ __global__ __launch_bounds__(64 * NW, DB ? 2 : 1) void mlp_f16x3(const MlpArgs a
             }
           }
           const unsigned mk = l3_row_max(l3_absmax8(v0[ct], v1[ct]));
-          enew[ct] = max(-100, min((int)((mk >> 23) & 255u) - 127, 128));   // 2^e <= max < 2^(e+1)
-          need = need || (enew[ct] > eset[ct] + 2);
+          enew[ct] = max(L3_EXP_MIN, min((int)((mk >> 23) & 255u) - 127, L3_EXP_MAX));   // 2^e <= max < 2^(e+1)
+          need = need || (enew[ct] > eset[ct] + L3_SCALE_MARGIN);
         }
+        // (f16x3.h's rule and numbers, its text in place: with the l3_scale_* calls the CT = 2 kernels get other registers)
         if (__builtin_amdgcn_ballot_w64(need) != 0) {              // rare after the first chunk
 #pragma unroll
           for (int ct = 0; ct < CT; ++ct) {
-            const bool mine = enew[ct] > eset[ct] + 2;
+            const bool mine = enew[ct] > eset[ct] + L3_SCALE_MARGIN;
             const int en = mine ? enew[ct] : eset[ct];
-            const float ratio = __builtin_bit_cast(float, (unsigned)(127 + max(eset[ct] - en, -126)) << 23);   // 2^(old - new) <= 1
+            const float ratio = __builtin_bit_cast(float, (unsigned)(127 + max(eset[ct] - en, L3_RATIO_MIN)) << 23);   // 2^(old - new) <= 1
 #pragma unroll
             for (int ob = 0; ob < NOB; ++ob) acc2[ob][ct] *= ratio;
             eset[ct] = en;
-            sh[ct] = __builtin_bit_cast(float, (unsigned)(127 + 12 - en) << 23);
-            sh_inv[ct] = __builtin_bit_cast(float, (unsigned)(127 - 12 + en) << 23);
+            sh[ct] = __builtin_bit_cast(float, (unsigned)(127 + L3_SCALE_SET - en) << 23);
+            sh_inv[ct] = __builtin_bit_cast(float, (unsigned)(127 - L3_SCALE_SET + en) << 23);
           }
         }
 #pragma unroll
@@ -480,7 +423,7 @@ __global__ __launch_bounds__(64 * NW, DB ? 2 : 1) void mlp_f16x3(const MlpArgs a
       }
       __builtin_amdgcn_sched_barrier(0);
 
-      ml_static_for<KS1, NBAT>(slot);
+      l3_static_for<KS1, NBAT>(slot);
     }
 
     // ---- y: D[i = feature][j = row]: a lane holds four consecutive features of its rows
@@ -604,6 +547,8 @@ __device__ __forceinline__ f32x4 ml_ps_fake_mfma(f16x8 a_, f16x8 b_, f32x4 c_) {
 #else
 #define ML_PS_MMA(a_, b_, c_) __builtin_amdgcn_mfma_f32_16x16x32_f16(a_, b_, c_, 0, 0, 0)
 #endif
+// (the kernel below issues its products through ML_PS_MMA, in l3_mfma3_pair's order -- f16x3.h -- spelled out: the helper has no hook
+// for the `mlp_trace_nomfma` build's fake)
 
 template <int KS1, int ACT>
 __global__ __launch_bounds__(512, 1) void mlp_f16x3_ps(const MlpArgs a) {
@@ -676,11 +621,7 @@ __global__ __launch_bounds__(512, 1) void mlp_f16x3_ps(const MlpArgs a) {
 #ifdef ML_PS_ABL
     if (ML_PS_ABL & 2) return;
 #endif
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const unsigned ah = addr + (unsigned)(q * 256);
-      asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3" : "=&v"(d[q][0]), "=&v"(d[q][1]) : "v"(ah), "v"(ah + pstride) : "memory");
-    }
+    l3_read4(d, addr, pstride);
   };
   const unsigned a1_lane = (unsigned)((g * 64 + j) * 16);        // W1 half-image: ((t 4 + g) 2 + part) 32 + 16 q + j units
   const unsigned a2_lane = (unsigned)((g * 2 * C + j) * 16);     // W2 half-image: (g 2 + part) C + 16 (2 t + q) + j units
@@ -833,7 +774,7 @@ __global__ __launch_bounds__(512, 1) void mlp_f16x3_ps(const MlpArgs a) {
       const int piece = (wave & 3) * 2 * UPH + v;
       const int i = piece * 64 + lane;
       const u32x4* src = (p & 1) ? a.W2p + ((size_t)c * HU + i) : a.W1p + ((size_t)(i >> 5) * Hd + 32 * c + (i & 31));
-      ml_glds16(src, dst0 + (unsigned)(piece * 1024));
+      l3_glds16(src, dst0 + (unsigned)(piece * 1024));
     }
   };
 
@@ -845,11 +786,11 @@ __global__ __launch_bounds__(512, 1) void mlp_f16x3_ps(const MlpArgs a) {
     read_batch(afr[0], a1, 512u);
     if constexpr (AR == 3) read_batch(afr[1], a1 + 4096u, 512u);
     acc1[0] = acc1[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    ml_static_for<0, KS1>([&](auto tc) __attribute__((always_inline)) {
+    l3_static_for<0, KS1>([&](auto tc) __attribute__((always_inline)) {
       constexpr int T = decltype(tc)::value;
       // AR == 3: batch T + 2 is requested behind the wait for batch T; AR == 2: batch T + 1 in front of it (its slot was batch T - 1's)
       if constexpr (AR == 2 && T + 1 < KS1) read_batch(afr[(T + 1) % AR], a1 + (unsigned)((T + 1) * 4096), 512u);
-      ml_wait_lgkm<(T + 1 < KS1 ? 4 : 0)>(afr[T % AR]);
+      l3_wait_lgkm<(T + 1 < KS1 ? 4 : 0)>(afr[T % AR]);
       if constexpr (AR == 3 && T + 2 < KS1) read_batch(afr[(T + 2) % AR], a1 + (unsigned)((T + 2) * 4096), 512u);
       __builtin_amdgcn_sched_barrier(0);
       const f16x8 ah0 = __builtin_bit_cast(f16x8, afr[T % AR][0][0]), am0 = __builtin_bit_cast(f16x8, afr[T % AR][0][1]);
@@ -879,16 +820,16 @@ __global__ __launch_bounds__(512, 1) void mlp_f16x3_ps(const MlpArgs a) {
       }
     }
     const unsigned mk = l3_row_max(l3_absmax8(v0, v1));
-    const int enew = max(-100, min((int)((mk >> 23) & 255u) - 127, 128));   // 2^e <= max < 2^(e+1)
-    const bool need = enew > eset + 2;
+    const int enew = l3_scale_exp(mk);
+    const bool need = l3_scale_stale(enew, eset);
     if (__builtin_amdgcn_ballot_w64(need) != 0) {                // rare after the first chunk
       const int en = need ? enew : eset;
-      const float ratio = __builtin_bit_cast(float, (unsigned)(127 + max(eset - en, -126)) << 23);   // 2^(old - new) <= 1
+      const float ratio = l3_scale_ratio(eset, en);
 #pragma unroll
       for (int ob = 0; ob < NOB; ++ob) acc2[ob] *= ratio;
       eset = en;
-      sh = __builtin_bit_cast(float, (unsigned)(127 + 12 - en) << 23);
-      sh_inv = __builtin_bit_cast(float, (unsigned)(127 - 12 + en) << 23);
+      sh = l3_scale_of(en);
+      sh_inv = l3_scale_inv_of(en);
     }
     l3_split8(v0, v1, sh, hh, hm);
     ML_TR(sl, 2);
@@ -901,11 +842,11 @@ __global__ __launch_bounds__(512, 1) void mlp_f16x3_ps(const MlpArgs a) {
     read_batch(afr[0], a2, (unsigned)(C * 16));
     if constexpr (AR == 3) read_batch(afr[1], a2 + 512u, (unsigned)(C * 16));
     if (next_half >= 0) request_half(next_half);
-    ml_static_for<0, KS1>([&](auto tc) __attribute__((always_inline)) {
+    l3_static_for<0, KS1>([&](auto tc) __attribute__((always_inline)) {
       constexpr int T = decltype(tc)::value;
       constexpr int B0 = 2 * T, B1 = B0 + 1;
       if constexpr (AR == 2 && T + 1 < KS1) read_batch(afr[(T + 1) % AR], a2 + (unsigned)((T + 1) * 512), (unsigned)(C * 16));
-      ml_wait_lgkm<(T + 1 < KS1 ? 4 : 0)>(afr[T % AR]);
+      l3_wait_lgkm<(T + 1 < KS1 ? 4 : 0)>(afr[T % AR]);
       if constexpr (AR == 3 && T + 2 < KS1) read_batch(afr[(T + 2) % AR], a2 + (unsigned)((T + 2) * 512), (unsigned)(C * 16));
       __builtin_amdgcn_sched_barrier(0);
       const f16x8 ah0 = __builtin_bit_cast(f16x8, afr[T % AR][0][0]), am0 = __builtin_bit_cast(f16x8, afr[T % AR][0][1]);
@@ -991,24 +932,24 @@ static int ml_launch(const MlpArgs& a, int act, hipStream_t st) {
   const int ngroups = (a.M + RG - 1) / RG;
   const size_t lds = (size_t)(DB ? 2 : 1) * 16 * C * 16 + (size_t)(2 * a.Hd + 6 * C) * 4;
   if (lds > 160 * 1024) return UNIVS_ERR_NOT_IMPLEMENTED;
-  const int abl = config().linear_ablate;                         // 2 / 3 / 4: timing experiments (encoder FFN and Swin stage 1 only)
-  if (abl >= 2 && abl <= 4 && ((KS1 == 8 && act == ML_ACT_RELU) || (KS1 == 3 && act == ML_ACT_GELU))) {
+  const int abl = config().linear_ablate;                         // LA_MLP_NO*: timing experiments (encoder FFN and Swin stage 1 only)
+  if (abl >= LA_MLP_NOMFMA && abl <= LA_MLP_NOACT && ((KS1 == 8 && act == ML_ACT_RELU) || (KS1 == 3 && act == ML_ACT_GELU))) {
     if constexpr (KS1 == 8) {
-      if (abl == 2) return ml_launch1<KS1, CT, ML_ACT_RELU, NW, 1>(a, lds, ngroups, st);
-      if (abl == 3) return ml_launch1<KS1, CT, ML_ACT_RELU, NW, 2>(a, lds, ngroups, st);
+      if (abl == LA_MLP_NOMFMA) return ml_launch1<KS1, CT, ML_ACT_RELU, NW, 1>(a, lds, ngroups, st);
+      if (abl == LA_MLP_NOREADS) return ml_launch1<KS1, CT, ML_ACT_RELU, NW, 2>(a, lds, ngroups, st);
       return ml_launch1<KS1, CT, ML_ACT_RELU, NW, 3>(a, lds, ngroups, st);
     }
     if constexpr (KS1 == 3) {
-      if (abl == 2) return ml_launch1<KS1, CT, ML_ACT_GELU, NW, 1>(a, lds, ngroups, st);
-      if (abl == 3) return ml_launch1<KS1, CT, ML_ACT_GELU, NW, 2>(a, lds, ngroups, st);
+      if (abl == LA_MLP_NOMFMA) return ml_launch1<KS1, CT, ML_ACT_GELU, NW, 1>(a, lds, ngroups, st);
+      if (abl == LA_MLP_NOREADS) return ml_launch1<KS1, CT, ML_ACT_GELU, NW, 2>(a, lds, ngroups, st);
       return ml_launch1<KS1, CT, ML_ACT_GELU, NW, 3>(a, lds, ngroups, st);
     }
   }
   if constexpr (DB && NW == 8 && CT == 1 && KS1 >= 4 && ML_GLDS) {
-    // the phase-shifted kernel (waves 4-7 half a chunk behind waves 0-3): UnivsConfig.linear_ablate = 10.  NOT the default: it measured
+    // the phase-shifted kernel (waves 4-7 half a chunk behind waves 0-3): UnivsConfig.linear_ablate = LA_MLP_PHASE_SHIFT.  NOT the default: it measured
     // 329 us against the lockstep kernel's 321 on the encoder FFN (profiles/r06_mlp_phase_shift_v1.txt) -- kept for A / B runs
     const size_t lds_ps = (size_t)4 * 8 * C * 16 + (size_t)(2 * a.Hd + 6 * C) * 4;
-    if (abl == 10 && lds_ps <= 160 * 1024) {
+    if (abl == LA_MLP_PHASE_SHIFT && lds_ps <= 160 * 1024) {
       MlpArgs b = a;
       b.nwg = std::min(cu_count(), ngroups);
       const void* fn = act == ML_ACT_RELU ? reinterpret_cast<const void*>(&mlp_f16x3_ps<KS1, ML_ACT_RELU>)

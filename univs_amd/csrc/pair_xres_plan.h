@@ -11,7 +11,6 @@ constexpr int PX_THREADS = 512;   // 8 waves, two per SIMD: one workgroup per CU
 constexpr int PX_ROWS = 128;      // rows of a group: 16 per wave
 constexpr int PX_CHUNK = 32;      // features of a W chunk (two MFMA feature blocks)
 constexpr int PX_IMAGES = 4;      // chunk images in LDS: the current chunk, the two after it, and the one being requested
-constexpr int PX_ABLATE_OFF = 11; // UnivsConfig.linear_ablate: the entry launches linear_pair_f16x3 (A / B)
 
 // bytes of LDS: PX_IMAGES chunk images [(K / 8) x 2 parts][32 features] of 16-byte units | bias and inverse scales of both problems
 inline size_t pair_xres_lds(int N_a, int N_b, int K) { return (size_t)PX_IMAGES * (K / 8) * 2 * PX_CHUNK * 16 + (size_t)2 * (N_a + N_b) * 4; }

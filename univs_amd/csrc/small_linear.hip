@@ -103,7 +103,7 @@ __global__ __launch_bounds__(64 * SL_WAVES, MERGE ? 2 : 3) void small_linear_ker
   if (tid < 32) (&rmax[0][0])[tid] = 0u;
   __syncthreads();
   constexpr int SLOTS = (SL_KMAX / 32) * 64 / (64 * SL_WAVES);  // per thread (1)
-  f32x4 xv[SLOTS][2], xw[SLOTS][2];
+  f32x4 xw[SLOTS][2], xv[SLOTS][2];                            // (in this order: the other one gives small_linear_kernel<false> other registers)
 #pragma unroll
   for (int i = 0; i < SLOTS; ++i) {
     const int s_ = tid + 64 * SL_WAVES * i;
@@ -176,22 +176,16 @@ __global__ __launch_bounds__(64 * SL_WAVES, MERGE ? 2 : 3) void small_linear_ker
   const u32x4* xt = xs + my_tile * tile_units + lane;
 
   // ---- the product
-  f32x4 acc[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
+  f32x4 acc[2][1];                                              // [block][the one column tile]: l3_mfma3_pair's form
+  acc[0][0] = acc[1][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
   for (int kb = 0; kb < KS; kb += SL_AHEAD) {
 #pragma unroll
     for (int u = 0; u < SL_AHEAD; ++u) {
       const int ks = kb + u;
       if (ks < KS) {                                            // uniform
-        const f16x8 bh = __builtin_bit_cast(f16x8, xt[ks * 64]), bm = __builtin_bit_cast(f16x8, xt[KS * 64 + ks * 64]);
-        const f16x8 ah0 = __builtin_bit_cast(f16x8, afr[u][0][0]), am0 = __builtin_bit_cast(f16x8, afr[u][0][1]);
-        const f16x8 ah1 = __builtin_bit_cast(f16x8, afr[u][1][0]), am1 = __builtin_bit_cast(f16x8, afr[u][1][1]);
-        acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am0, bh, acc[0], 0, 0, 0);   // smallest terms first
-        acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am1, bh, acc[1], 0, 0, 0);
-        acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, bm, acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, bm, acc[1], 0, 0, 0);
-        acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, bh, acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, bh, acc[1], 0, 0, 0);
+        const f16x8 bh[1] = {__builtin_bit_cast(f16x8, xt[ks * 64])}, bm[1] = {__builtin_bit_cast(f16x8, xt[KS * 64 + ks * 64])};
+        l3_mfma3_pair<1>(afr[u], bh, bm, acc[0], acc[1]);
         __builtin_amdgcn_sched_barrier(0);                       // (the refill below overwrites the fragments just consumed: no copies)
         if (ks + SL_AHEAD < KS) load_a(ks + SL_AHEAD, afr[u]);
         __builtin_amdgcn_sched_barrier(0);
@@ -206,7 +200,7 @@ __global__ __launch_bounds__(64 * SL_WAVES, MERGE ? 2 : 3) void small_linear_ker
   for (int q = 0; q < 2; ++q) {
     const int f = f0 + 16 * q + 4 * g;
     const bool ok = f < N;
-    f32x4 t = (acc[q] * sx_inv) * e_wi[q] + e_bi[q];
+    f32x4 t = (acc[q][0] * sx_inv) * e_wi[q] + e_bi[q];
     if (a.relu) t = __builtin_elementwise_maximum(t, (f32x4){0.f, 0.f, 0.f, 0.f});   // NaN-propagating, as torch.relu
     t += e_res[q];
     v[q] = ok ? t : (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -417,21 +411,15 @@ __global__ __launch_bounds__(64 * SL_WAVES, 3) void small_chain_kernel(const SlC
       e_wi[q] = *reinterpret_cast<const f32x4*>(a.winv[st] + f);
       e_bi[q] = a.bias[st] ? *reinterpret_cast<const f32x4*>(a.bias[st] + f) : (f32x4){0.f, 0.f, 0.f, 0.f};
     }
-    f32x4 acc[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
+    f32x4 acc[2][1];
+    acc[0][0] = acc[1][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int kb = 0; kb < KS; kb += SL_AHEAD) {
 #pragma unroll
       for (int u = 0; u < SL_AHEAD; ++u) {
         const int ks = kb + u;
-        const f16x8 bh = __builtin_bit_cast(f16x8, xt[ks * 64]), bm = __builtin_bit_cast(f16x8, xt[KS * 64 + ks * 64]);
-        const f16x8 ah0 = __builtin_bit_cast(f16x8, afr[u][0][0]), am0 = __builtin_bit_cast(f16x8, afr[u][0][1]);
-        const f16x8 ah1 = __builtin_bit_cast(f16x8, afr[u][1][0]), am1 = __builtin_bit_cast(f16x8, afr[u][1][1]);
-        acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am0, bh, acc[0], 0, 0, 0);   // smallest terms first
-        acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(am1, bh, acc[1], 0, 0, 0);
-        acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, bm, acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, bm, acc[1], 0, 0, 0);
-        acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, bh, acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, bh, acc[1], 0, 0, 0);
+        const f16x8 bh[1] = {__builtin_bit_cast(f16x8, xt[ks * 64])}, bm[1] = {__builtin_bit_cast(f16x8, xt[KS * 64 + ks * 64])};
+        l3_mfma3_pair<1>(afr[u], bh, bm, acc[0], acc[1]);
         __builtin_amdgcn_sched_barrier(0);
         if (ks + SL_AHEAD < KS) load_a(wl, ks + SL_AHEAD, afr[u]);
         else if (st + 1 < a.stages) load_a(a.Wp[st + 1] + wl_off, ks + SL_AHEAD - KS, afr[u]);   // the next stage's first fragments
@@ -440,7 +428,7 @@ __global__ __launch_bounds__(64 * SL_WAVES, 3) void small_chain_kernel(const SlC
     }
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-      f32x4 t = (acc[q] * sx_inv) * e_wi[q] + e_bi[q];
+      f32x4 t = (acc[q][0] * sx_inv) * e_wi[q] + e_bi[q];
       if (a.relu[st]) t = __builtin_elementwise_maximum(t, (f32x4){0.f, 0.f, 0.f, 0.f});
       v[q] = t;
     }
