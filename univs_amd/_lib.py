@@ -1,6 +1,7 @@
 """ctypes binding of libunivs_hip.so (the C ABI declared in include/univs_hip.h, include/univs_eval_hip.h,
 include/univs_fused_hip.h, include/univs_pvos_hip.h, include/univs_semantic_hip.h, include/univs_encoder_hip.h,
-include/univs_swin_hip.h, include/univs_frames_hip.h, include/univs_prompts_hip.h and include/univs_png_hip.h).
+include/univs_swin_hip.h, include/univs_frames_hip.h, include/univs_prompts_hip.h, include/univs_png_hip.h and
+include/univs_hota_hip.h).
 
 The header is the one statement of the ABI: `SIGNATURES` (restype / argtypes of every `univs_*` symbol) and `CONFIG_FIELDS` (the
 members of `struct UnivsConfig`) are read from its text when this module loads -- no table is kept by hand.
@@ -111,6 +112,10 @@ with open(PROMPTS_HEADER_PATH) as _f:
 PNG_HEADER_PATH = os.path.join(_HERE, "..", "include", "univs_png_hip.h")
 with open(PNG_HEADER_PATH) as _f:
     PNG_SIGNATURES = parse_signatures(_f.read())
+# The eleventh header (include/univs_hota_hip.h: the HOTA tables of a video and the batched assignment solver), likewise.
+HOTA_HEADER_PATH = os.path.join(_HERE, "..", "include", "univs_hota_hip.h")
+with open(HOTA_HEADER_PATH) as _f:
+    HOTA_SIGNATURES = parse_signatures(_f.read())
 
 _lib = None
 
@@ -132,7 +137,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (*SIGNATURES.items(), *EVAL_SIGNATURES.items(), *FUSED_SIGNATURES.items(),
                               *PVOS_SIGNATURES.items(), *SEMANTIC_SIGNATURES.items(), *ENCODER_SIGNATURES.items(), *SWIN_SIGNATURES.items(),
-                              *FRAMES_SIGNATURES.items(), *PROMPTS_SIGNATURES.items(), *PNG_SIGNATURES.items()):
+                              *FRAMES_SIGNATURES.items(), *PROMPTS_SIGNATURES.items(), *PNG_SIGNATURES.items(), *HOTA_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing -> loud
         fn.restype = res
         fn.argtypes = args

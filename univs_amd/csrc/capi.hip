@@ -9,6 +9,7 @@
 #include "../../include/univs_eval_hip.h"
 #include "../../include/univs_frames_hip.h"
 #include "../../include/univs_fused_hip.h"
+#include "../../include/univs_hota_hip.h"
 #include "../../include/univs_png_hip.h"
 #include "../../include/univs_prompts_hip.h"
 #include "../../include/univs_pvos_hip.h"
@@ -976,6 +977,30 @@ int univs_png_deflate_maps(const void* src, int src_is_i32, int N, int H, int W,
   if (!src || !scratch || !out || !offsets) return e.null_pointer();
   return e.covered(png_deflate_maps(src, src_is_i32, N, H, W, lut, K, C, rows_per_stripe, scratch, out, offsets, e.st),
                    "not covered (C in {1, 3}, rows_per_stripe (W C + 1) <= 24576, N H (W C + 1) < 2^31)");
+}
+
+// (include/univs_hota_hip.h)
+int univs_hota_counts(const int32_t* inter, const int32_t* gt_area, const int32_t* tr_area, int D, int G, int T, const int32_t* gt_ids,
+                      const int32_t* gt_starts, const int32_t* tr_ids, const int32_t* tr_starts, int C, int max_g, int max_p,
+                      const double* thresholds, int A, int32_t* tp_fn_fp, int32_t* matches, double* loca_sum, int32_t* gt_id_count,
+                      int32_t* tracker_id_count, int32_t* match_col, void* stream) {
+  const Entry e("univs_hota_counts", stream);
+  if (D < 1 || G < 1 || T < 1 || C < 1 || A < 1 || max_g < 0 || max_p < 0)
+    return e.invalid("bad arguments D=%d G=%d T=%d C=%d max_g=%d max_p=%d A=%d", D, G, T, C, max_g, max_p, A);
+  if (!inter || !gt_area || !tr_area || !gt_ids || !gt_starts || !tr_ids || !tr_starts || !thresholds || !tp_fn_fp || !matches || !loca_sum ||
+      !gt_id_count || !tracker_id_count || !match_col)
+    return e.null_pointer();
+  return e.covered(hota_counts(inter, gt_area, tr_area, D, G, T, gt_ids, gt_starts, tr_ids, tr_starts, C, max_g, max_p, thresholds, A, tp_fn_fp,
+                               matches, loca_sum, gt_id_count, tracker_id_count, match_col, e.st),
+                   "not covered (at most 64 ids per side of a class, A <= 32, T <= 65535, D G T < 2^31)");
+}
+
+int univs_lsa_max_f64(const double* score, const int32_t* rows, const int32_t* cols, int B, int32_t* col_of_row, void* stream) {
+  const Entry e("univs_lsa_max_f64", stream);
+  if (B < 0) return e.invalid("bad arguments B=%d", B);
+  if (B == 0) return UNIVS_OK;
+  if (!score || !rows || !cols || !col_of_row) return e.null_pointer();
+  return lsa_max_f64(score, rows, cols, B, col_of_row, e.st);
 }
 
 // The two window-attention entries on image-layout operands share their checks

@@ -240,4 +240,10 @@ int resize_rle_masks_u8(const int* bounds, const int* starts, long long n_bounds
 int png_deflate_maps(const void* src, int src_is_i32, int N, int H, int W, const unsigned char* lut, int K, int C, int rows_per_stripe,
                      unsigned char* scratch, unsigned char* out, long long* offsets, hipStream_t st);
 
+// ---- hota_count.hip: return UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the sizes are not covered, or the launch's error
+int hota_counts(const int* inter, const int* gt_area, const int* tr_area, int D, int G, int T, const int* gt_ids, const int* gt_starts,
+                const int* tr_ids, const int* tr_starts, int C, int max_g, int max_p, const double* thr, int A, int* tp_fn_fp, int* matches,
+                double* loca_sum, int* gt_id_count, int* tracker_id_count, int* match_col, hipStream_t st);
+int lsa_max_f64(const double* score, const int* rows, const int* cols, int B, int* col_of_row, hipStream_t st);
+
 }  // namespace univs

@@ -2,12 +2,13 @@
 
     python -m univs_amd.run --config-file F --weights W (--json J --image-root R --dataset-name N | --video-dir D) --output-dir O
                             [--resize gpu|host] [--png host|gpu]
-                            [--gt-json G | --pan-gt-json P --truth-dir T | --davis-root V | --pvos-data V]
+                            [--gt-json G [--hota] | --pan-gt-json P --truth-dir T | --davis-root V | --pvos-data V]
                             [KEY VALUE ...]
 
 The model is `build_model(load_cfg(F, [KEY VALUE ...]))` with `ckpt["model"]` loaded strictly (the reference's state-dict layout).  The
 frames are the videos of a YouTube-VIS-format file, or the sub-folders of a folder of jpg / png frames (data/datasets.py), mapped by
 data.VideoTestMapper.  With --gt-json the outputs go to evaluation.YTVISEvaluator (results.json; AP / AR when the file has annotations),
+or with --hota to evaluation.hota.HOTAEvaluator (results.json, hota-final.txt),
 with --pan-gt-json and --truth-dir to evaluation.VPSEvaluator; without either each video's driver output is saved to O/<video_id>.pt.
 
 A --dataset-name of a video-object-segmentation data set (sot_*, mots_mose*, mots_burst*, pvos_*) reads the file with
@@ -47,6 +48,7 @@ def parse_args(argv=None):
     ap.add_argument("--png", choices=("host", "gpu"), default="host", help="who compresses the result PNGs: Pillow, or the HIP encoder")
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--gt-json", help="YouTube-VIS annotation file: score with YTVISEvaluator")
+    ap.add_argument("--hota", action="store_true", help="with --gt-json: score with HOTAEvaluator instead of YTVISEvaluator")
     ap.add_argument("--pan-gt-json", help="VIPSeg panoptic ground-truth json: score with VPSEvaluator (with --truth-dir)")
     ap.add_argument("--truth-dir", help="the folder of the ground-truth panoptic PNGs")
     ap.add_argument("--davis-root", help="the DAVIS folder (Annotations/, ImageSets/): score a sot_davis* run with DAVISEvaluator")
@@ -62,6 +64,8 @@ def parse_args(argv=None):
         ap.error("--pan-gt-json and --truth-dir go together")
     if sum(v is not None for v in (args.gt_json, args.pan_gt_json, args.davis_root, args.pvos_data)) > 1:
         ap.error("one evaluator at a time: --gt-json, --pan-gt-json, --davis-root or --pvos-data")
+    if args.hota and args.gt_json is None:
+        ap.error("--hota scores against --gt-json")
     args.vos = bool(from_json and is_vos_name(args.dataset_name))
     if (args.davis_root or args.pvos_data) and not args.vos:
         ap.error("--davis-root and --pvos-data score a VOS data set (--dataset-name sot_*, mots_mose*, mots_burst*, pvos_*)")
@@ -73,6 +77,9 @@ def parse_args(argv=None):
 
 
 def build_evaluator(args):
+    if args.gt_json and getattr(args, "hota", False):
+        from .evaluation.hota import HOTAEvaluator
+        return HOTAEvaluator(args.gt_json, output_dir=args.output_dir, device=args.device)
     if args.gt_json:
         from .evaluation.ytvis import YTVISEvaluator
         return YTVISEvaluator(args.gt_json, output_dir=args.output_dir, device=args.device)
