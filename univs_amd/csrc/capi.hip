@@ -11,6 +11,7 @@
 #include "../../include/univs_fused_hip.h"
 #include "../../include/univs_hota_hip.h"
 #include "../../include/univs_png_hip.h"
+#include "../../include/univs_pngread_hip.h"
 #include "../../include/univs_prompts_hip.h"
 #include "../../include/univs_pvos_hip.h"
 #include "../../include/univs_semantic_hip.h"
@@ -977,6 +978,21 @@ int univs_png_deflate_maps(const void* src, int src_is_i32, int N, int H, int W,
   if (!src || !scratch || !out || !offsets) return e.null_pointer();
   return e.covered(png_deflate_maps(src, src_is_i32, N, H, W, lut, K, C, rows_per_stripe, scratch, out, offsets, e.st),
                    "not covered (C in {1, 3}, rows_per_stripe (W C + 1) <= 24576, N H (W C + 1) < 2^31)");
+}
+
+// (include/univs_pngread_hip.h)
+int univs_png_read(const uint8_t* streams, const long long* stream_offsets, const int* desc, const uint8_t* palettes, int P,
+                   const long long* filt_offsets, const long long* out_offsets, int N, long long streams_total, long long filt_total,
+                   long long out_total, int max_rowbytes, uint8_t* filtered, uint8_t* out, int* status, void* stream) {
+  const Entry e("univs_png_read", stream);
+  if (N < 0 || P < 0 || streams_total < 0 || filt_total < 0 || out_total < 0 || max_rowbytes < 1 || (P > 0 && !palettes))
+    return e.invalid("bad arguments N=%d P=%d palettes=%s streams_total=%lld filt_total=%lld out_total=%lld max_rowbytes=%d", N, P,
+                     palettes ? "given" : "NULL", streams_total, filt_total, out_total, max_rowbytes);
+  if (N == 0) return UNIVS_OK;
+  if (!streams || !stream_offsets || !desc || !filt_offsets || !out_offsets || !filtered || !out || !status) return e.null_pointer();
+  return e.covered(png_read(streams, stream_offsets, desc, palettes, P, filt_offsets, out_offsets, N, streams_total, filt_total, out_total,
+                            max_rowbytes, filtered, out, status, e.st),
+                   "not covered (max_rowbytes <= 24576, streams_total, filt_total and out_total < 2^31)");
 }
 
 // (include/univs_hota_hip.h)

@@ -240,6 +240,11 @@ int resize_rle_masks_u8(const int* bounds, const int* starts, long long n_bounds
 int png_deflate_maps(const void* src, int src_is_i32, int N, int H, int W, const unsigned char* lut, int K, int C, int rows_per_stripe,
                      unsigned char* scratch, unsigned char* out, long long* offsets, hipStream_t st);
 
+// ---- png_inflate.hip: returns UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the sizes are not covered, or the launch's error
+int png_read(const unsigned char* streams, const long long* stream_offsets, const int* desc, const unsigned char* palettes, int P,
+             const long long* filt_offsets, const long long* out_offsets, int N, long long streams_total, long long filt_total,
+             long long out_total, int max_rowbytes, unsigned char* filtered, unsigned char* out, int* status, hipStream_t st);
+
 // ---- hota_count.hip: return UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the sizes are not covered, or the launch's error
 int hota_counts(const int* inter, const int* gt_area, const int* tr_area, int D, int G, int T, const int* gt_ids, const int* gt_starts,
                 const int* tr_ids, const int* tr_starts, int C, int max_g, int max_p, const double* thr, int A, int* tp_fn_fp, int* matches,

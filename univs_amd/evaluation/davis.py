@@ -30,7 +30,7 @@ import warnings
 import numpy as np
 import torch
 
-from ._counts import pick_device as _device, read_png as _read
+from ._counts import check_reader, device_stack, pick_device as _device, read_png as _read
 from .davis_counts import davis_counts
 
 SUBSET_OPTIONS = ("train", "val", "test-dev", "test-challenge")
@@ -117,11 +117,13 @@ def list_sequences(davis_root, task, subset="val", sequences="all", resolution="
     return names
 
 
-def read_sequence(davis_root, seq, task, resolution="480p"):
+def read_sequence(davis_root, seq, task, resolution="480p", reader="host", device=None):
     """(maps uint8 [T, H, W], frame ids) of one sequence: the sorted `*.png` files of Annotations[_unsupervised]/<resolution>/<seq>, raw
     (255 = void is still in them).  JPEGImages/<resolution>/<seq>/*.jpg must exist and fixes the frame count: fewer annotations than
     images is a FileNotFoundError here (the reference fails on the missing file's placeholder).  A frame id is the file name without
-    its extension and without dots.  Frames of another size than the first are a ValueError, as the reference's array assignment."""
+    its extension and without dots.  Frames of another size than the first are a ValueError, as the reference's array assignment.
+    reader "gpu": the maps are decoded on the device and returned as a device tensor (`_counts.device_stack`; files it does not take go
+    through the loop below)."""
     img_path, mask_path, _ = _paths(davis_root, task, "val", resolution)
     images = sorted(glob.glob(os.path.join(img_path, seq, "*.jpg")))
     if not images:
@@ -129,6 +131,9 @@ def read_sequence(davis_root, seq, task, resolution="480p"):
     masks = sorted(glob.glob(os.path.join(mask_path, seq, "*.png")))
     if len(masks) < len(images):
         raise FileNotFoundError(f"{len(masks)} annotations for the {len(images)} images of {os.path.join(mask_path, seq)}")
+    stack = device_stack(masks, reader, device)
+    if stack is not None:
+        return stack, ["".join(m.split("/")[-1].split(".")[:-1]) for m in masks]
     maps, ids = [], []
     for m in masks:
         a = _read(m)
@@ -139,9 +144,12 @@ def read_sequence(davis_root, seq, task, resolution="480p"):
     return np.stack(maps), ids
 
 
-def read_results(res_path, seq, frame_ids):
+def read_results(res_path, seq, frame_ids, reader="host", device=None):
     """uint8 [T, H, W]: `<res_path>/<seq>/<frame id>.png` of every id (results.py:11-26).  A file that cannot be read ends the run
-    (SystemExit), a frame of another size than the first is a ValueError."""
+    (SystemExit), a frame of another size than the first is a ValueError.  reader "gpu": as in `read_sequence`."""
+    stack = device_stack([os.path.join(res_path, seq, f"{fid}.png") for fid in frame_ids], reader, device)
+    if stack is not None:
+        return stack
     maps = []
     for fid in frame_ids:
         path = os.path.join(res_path, seq, f"{fid}.png")
@@ -165,7 +173,10 @@ def sequence_tables(gt, pred, task, metrics=("J", "F"), device=None, bound_th=0.
     `_evaluate_unsupervised` return them (vos_davis_evaluation.py:198-239).  gt uint8 [T, H, W] raw (with its 255s, all frames), pred
     uint8 [T', H', W'] the result frames that the task reads (T' = T - 2 in the semi-supervised task).  One upload of the two stacks,
     one `davis_counts` call, one transfer of the counts back."""
-    G = int(np.where(gt[0] == VOID_LABEL, 0, gt[0]).max())           # the first frame of the whole sequence decides
+    if isinstance(gt, torch.Tensor) != isinstance(pred, torch.Tensor):              # (reader "gpu" and one side went through the host loop)
+        gt, pred = (x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in (gt, pred))
+    on_device = isinstance(gt, torch.Tensor)                         # (reader "gpu": both stacks are there already)
+    G = int((gt[0] * (gt[0] != VOID_LABEL)).max()) if on_device else int(np.where(gt[0] == VOID_LABEL, 0, gt[0]).max())   # the first frame of the whole sequence decides
     if task == "semi-supervised":
         gt = gt[1:-1]
     P = int(pred.max())
@@ -179,11 +190,14 @@ def sequence_tables(gt, pred, task, metrics=("J", "F"), device=None, bound_th=0.
     if G == 0:
         return np.zeros((0, T)), np.zeros((0, T))
     if "J" in metrics or "F" in metrics:
-        assert gt.shape == pred.shape, f"Annotation({gt.shape}) and segmentation:{pred.shape} dimensions do not match."
+        assert gt.shape == pred.shape, f"Annotation({tuple(gt.shape)}) and segmentation:{tuple(pred.shape)} dimensions do not match."
     Pp = max(P, G)                                                   # missing result objects are empty masks
     device = _device(device)
-    counts = davis_counts(torch.as_tensor(np.ascontiguousarray(gt)).to(device), torch.as_tensor(np.ascontiguousarray(pred)).to(device),
-                          G, Pp, disk_radius(gt.shape[1], gt.shape[2], bound_th), task == "unsupervised")
+    if on_device:
+        g_dev, p_dev = gt.contiguous().to(device), pred.contiguous().to(device)
+    else:
+        g_dev, p_dev = torch.as_tensor(np.ascontiguousarray(gt)).to(device), torch.as_tensor(np.ascontiguousarray(pred)).to(device)
+    counts = davis_counts(g_dev, p_dev, G, Pp, disk_radius(gt.shape[1], gt.shape[2], bound_th), task == "unsupervised")
     flat = torch.cat([c.reshape(-1) for c in counts]).cpu().numpy()
     sizes = [int(c.numel()) for c in counts]
     parts = np.split(flat, np.cumsum(sizes)[:-1])
@@ -215,16 +229,17 @@ def metrics_text(metrics_res):
 
 
 def evaluate_davis_files(davis_root, res_path, task, subset="val", sequences="all", resolution="480p", metrics=("J", "F"), device=None,
-                         output_dir=None):
+                         output_dir=None, reader="host"):
     """`evaluate_davis` on a DAVIS tree and a result directory `<res_path>/<seq>/<frame id>.png`: {"J": {"M", "R", "D": one entry per
     scored object, "M_per_object": {"<seq>_<k>": mean}}, "F": the same}.  Every PNG is read once; a sequence's two stacks are uploaded
     once to `device` (default: the GPU when there is one, else the ATen counts on the CPU).  Writes davis-metrics.txt into `output_dir`
-    when it is given.
+    when it is given.  reader "gpu": the PNGs are decoded on the device (`_counts.device_stack`) instead of by Pillow.
 
     Errors as the reference's: SystemExit for a result frame that cannot be read, a result id above the number of gt objects
     (semi-supervised) or above 20 (unsupervised); AssertionError for result frames of another size than the annotations;
     FileNotFoundError for a missing tree; NameError for the unsupervised task with one metric only."""
     metrics = tuple(metrics) if isinstance(metrics, (tuple, list)) else (metrics,)
+    check_reader(reader)
     if "T" in metrics:
         raise ValueError("Temporal metric not supported!")
     if "J" not in metrics and "F" not in metrics:
@@ -234,11 +249,11 @@ def evaluate_davis_files(davis_root, res_path, task, subset="val", sequences="al
         if m in metrics:
             metrics_res[m] = {"M": [], "R": [], "D": [], "M_per_object": {}}
     for seq in list_sequences(davis_root, task, subset, sequences, resolution):
-        gt, ids = read_sequence(davis_root, seq, task, resolution)
+        gt, ids = read_sequence(davis_root, seq, task, resolution, reader, device)
         if task == "semi-supervised":
             ids = ids[1:-1]
         ids[0]                                                       # (no frame left: the reference's IndexError)
-        pred = read_results(res_path, seq, ids)
+        pred = read_results(res_path, seq, ids, reader, device)
         j, f = sequence_tables(gt, pred, task, metrics, device)
         for ii in range(j.shape[0]):
             for m, table in (("J", j), ("F", f)):
@@ -263,7 +278,9 @@ class DAVISEvaluator:
     semi-supervised task at Full-Resolution in `<image_root minus two components>`.  `process` is empty, as in the reference: the
     driver has already written the PNGs to `<output_dir>/Annotations`."""
 
-    def __init__(self, dataset_name, image_root, tasks=None, output_dir=None, gt_set="val", sequences="all", metrics=("J", "F"), device=None):
+    def __init__(self, dataset_name, image_root, tasks=None, output_dir=None, gt_set="val", sequences="all", metrics=("J", "F"), device=None,
+                 reader="host"):
+        self.reader = check_reader(reader)                           # ("host" | "gpu": who decodes the PNGs, _counts.device_stack)
         if "refdavis" in dataset_name:
             inferred, self.resolution = "unsupervised", "480p"
             self.gt_root = "/".join(image_root.split("/")[:-2] + ["DAVIS"])
@@ -295,7 +312,7 @@ class DAVISEvaluator:
         """`evaluate_davis` on `<output_dir>/Annotations`; davis-metrics.txt into `output_dir`.  Returns the metrics dictionary (the
         reference returns nothing)."""
         res = evaluate_davis_files(self.gt_root, os.path.join(self._output_dir, "Annotations"), self.task, self.subset, self.sequences,
-                                   self.resolution, self.metrics, self.device, self._output_dir)
+                                   self.resolution, self.metrics, self.device, self._output_dir, reader=self.reader)
         for m_res in res.values():
             for k in ("M", "R", "D"):
                 print("{}: {:.2f}".format(k, sum(m_res[k]) / len(m_res[k]) * 100.))
@@ -311,8 +328,9 @@ def main(argv=None):
     ap.add_argument("--resolution", default="480p", help="480p or Full-Resolution")
     ap.add_argument("--output_dir", default=None, help="where davis-metrics.txt goes (default: it is not written)")
     ap.add_argument("--device", default=None, help="cuda / cpu (default: the GPU when there is one)")
+    ap.add_argument("--reader", default="host", choices=("host", "gpu"), help="who decodes the PNGs: Pillow on the host, or the device")
     a = ap.parse_args(argv)
-    r = evaluate_davis_files(a.davis_root, a.res_path, a.task, a.subset, "all", a.resolution, ("J", "F"), a.device, a.output_dir)
+    r = evaluate_davis_files(a.davis_root, a.res_path, a.task, a.subset, "all", a.resolution, ("J", "F"), a.device, a.output_dir, reader=a.reader)
     for m, m_res in r.items():
         print(m, *("{}: {:.2f}".format(k, sum(m_res[k]) / len(m_res[k]) * 100.) for k in ("M", "R", "D")))
     return r

@@ -23,7 +23,7 @@ the decay is fitted over fewer than 60 tracked objects; pvos-ious.txt has no lin
 One difference: a frame whose annotation and result differ in size raises ValueError whenever the video tracks an object at that
 frame.  The reference raises the same type, but only once an object is non-empty on both sides there.
 
-`python -m univs_amd.evaluation.pvos --res_path ... --data_path ... [--eval_decay]` scores a result directory.  Single process.
+`python -m univs_amd.evaluation.pvos --res_path ... --data_path ... [--eval_decay] [--reader host|gpu]` scores a result directory.  Single process.
 """
 import argparse
 import json
@@ -35,7 +35,7 @@ from glob import glob
 import numpy as np
 import torch
 
-from ._counts import pick_device as _device
+from ._counts import check_reader, device_stack, pick_device as _device, stack as _stack
 from .pvos_counts import dilation, pvos_counts
 
 # The class partition of VIPOSeg and the videos whose class 98 ("other machine") is unseen: facts of the dataset
@@ -118,18 +118,20 @@ def video_counts(labels, preds, tracked, device=None):
         K = max((int(x) for i in frames for x in tracked[i] if int(x) <= 255), default=0)
         if K == 0:
             continue
-        gt = torch.as_tensor(np.stack([labels[i] for i in frames])).to(device)
-        pr = torch.as_tensor(np.stack([preds[i] for i in frames])).to(device)
+        gt = torch.as_tensor(_stack([labels[i] for i in frames])).to(device)
+        pr = torch.as_tensor(_stack([preds[i] for i in frames])).to(device)
         counts = pvos_counts(gt, pr, dilation(H, W), K).cpu().numpy().astype(np.int64)
         for n, i in enumerate(frames):
             out[i] = counts[n]
     return out
 
 
-def eval_iou(res_list, seq_list, ref_list, obj_class_dict, eval_decay=False, device=None, details=None):
+def eval_iou(res_list, seq_list, ref_list, obj_class_dict, eval_decay=False, device=None, details=None, reader="host"):
     """The reference's `eval_iou`: the dictionary of the eight group means, their four averages, `overall_iou` and, with `eval_decay`,
     `decay`.  `details`, a dictionary, receives the per-object values behind them in the order of scoring: "<group>_miou" and
-    "<group>_biou" (lists), "decay" ({tracked objects: [(miou + biou) / 2]}) and "objects" ([(video, frame index, id)])."""
+    "<group>_biou" (lists), "decay" ({tracked objects: [(miou + biou) / 2]}) and "objects" ([(video, frame index, id)]).
+    reader "gpu": a video's ground truth and results are decoded on the device (`_counts.device_stack`), one call per side."""
+    check_reader(reader)
     miou_lists = {g: [] for g in GROUPS}
     biou_lists = {g: [] for g in GROUPS}
     iou_decay_dict = {i: [] for i in range(MAX_TRACKED)} if eval_decay else {}
@@ -144,8 +146,10 @@ def eval_iou(res_list, seq_list, ref_list, obj_class_dict, eval_decay=False, dev
         ann_list = sorted(glob(f + "/*"))
         ann_name_list = [x.split("/")[-1] for x in ann_list]
         assert len(label_list) == len(pred_list), "incomplete label/pred"
-        labels = [_read_u8(p) for p in label_list]
-        preds = [_read_u8(p) for p in pred_list]
+        labels, preds = device_stack(label_list, reader, device), device_stack(pred_list, reader, device)
+        if labels is None or preds is None or labels.shape[1:] != preds.shape[1:]:
+            labels = [_read_u8(p) for p in label_list]
+            preds = [_read_u8(p) for p in pred_list]
         obj_ids, tracked = [], []
         for i in range(len(label_list)):
             tracked.append(list(obj_ids))
@@ -206,15 +210,16 @@ def _lists(res_path, data_path):
     return res_list, seq_list, ref_list, obj_class_dict
 
 
-def evaluate_pvos_files(res_path, data_path, eval_decay=False, device=None, details=None):
+def evaluate_pvos_files(res_path, data_path, eval_decay=False, device=None, details=None, reader="host"):
     """The scores of the result directory `<res_path>/<video>/<frame>.png` against the VIPOSeg split `data_path` (Annotations_gt,
     Annotations, obj_class.json): the reference's dictionary.  Every PNG is read once; a video's two stacks are uploaded once to
-    `device` (default: the GPU when there is one, else the ATen counts on the CPU).
+    `device` (default: the GPU when there is one, else the ATen counts on the CPU).  reader "gpu": the id maps are decoded on the
+    device instead of by Pillow (the reference frames' ids stay with Pillow: a few files per video).
 
     Errors as the reference's: AssertionError for no result, for a result count that the references do not match, and for a video with
     unequal frame counts; KeyError for an id without a class and for 80 tracked objects with the decay on; ValueError for a frame
     whose two maps differ in size while an object is tracked (module docstring)."""
-    return eval_iou(*_lists(res_path, data_path), eval_decay, device, details)
+    return eval_iou(*_lists(res_path, data_path), eval_decay, device, details, reader)
 
 
 def scores_text(res_dict):
@@ -227,11 +232,12 @@ class PVOSEvaluator:
     detectron2's MetadataCatalog: the split is `image_root` minus its last component.  `process` is empty, as in the reference: the
     driver has already written the PNGs to `<output_dir>/Annotations`."""
 
-    def __init__(self, dataset_name, image_root, tasks=None, distributed=True, output_dir=None, device=None):
+    def __init__(self, dataset_name, image_root, tasks=None, distributed=True, output_dir=None, device=None, reader="host"):
         self._logger = logging.getLogger(__name__)
         self.dataset_name, self._tasks, self._distributed, self._output_dir, self.device = dataset_name, tasks, distributed, output_dir, device
         self.data_path = "/".join(image_root.split("/")[:-1])
         self.eval_decay = True
+        self.reader = check_reader(reader)                           # ("host" | "gpu": who decodes the PNGs, _counts.device_stack)
 
     def reset(self):
         os.makedirs(os.path.join(self._output_dir, "Annotations"), exist_ok=True)
@@ -242,7 +248,8 @@ class PVOSEvaluator:
     def evaluate(self):
         """`eval_iou` on `<output_dir>/Annotations` with the decay; pvos-ious.txt into `output_dir`.  Returns the dictionary (the
         reference returns nothing)."""
-        res_dict = evaluate_pvos_files(os.path.join(self._output_dir, "Annotations"), self.data_path, self.eval_decay, self.device)
+        res_dict = evaluate_pvos_files(os.path.join(self._output_dir, "Annotations"), self.data_path, self.eval_decay, self.device,
+                                       reader=self.reader)
         self._logger.info("Evaluation results for {}: \n".format(self.dataset_name))
         with open(os.path.join(self._output_dir, "pvos-ious.txt"), "w") as fh:
             fh.write(scores_text(res_dict))
@@ -259,8 +266,9 @@ def main(argv=None):
     ap.add_argument("--res_path", type=str, required=True, help="the result directory: <video>/<frame>.png")
     ap.add_argument("--eval_decay", action="store_true")
     ap.add_argument("--device", default=None, help="cuda / cpu (default: the GPU when there is one)")
+    ap.add_argument("--reader", default="host", choices=("host", "gpu"), help="who decodes the PNGs: Pillow on the host, or the device")
     a = ap.parse_args(argv)
-    res_dict = evaluate_pvos_files(a.res_path, a.data_path, a.eval_decay, a.device)
+    res_dict = evaluate_pvos_files(a.res_path, a.data_path, a.eval_decay, a.device, reader=a.reader)
     for k in res_dict:
         print("{}: {:.2f}".format(k, res_dict[k] * 100 if "iou" in k else res_dict[k]))
     return res_dict

@@ -26,6 +26,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
+from ._counts import check_reader, device_stack
 from .pair_counts import pair_counts
 
 VOID = 0
@@ -385,18 +386,24 @@ def _by_video(jsons):
     return {a["video_id"]: a["annotations"] for a in jsons["annotations"]}
 
 
-def _tables_from_files(video, gt_frames, pred_frames, submit_dir, truth_dir, device):
+def _tables_from_files(video, gt_frames, pred_frames, submit_dir, truth_dir, device, reader="host"):
+    """reader "gpu": both sides are decoded on the device as RGB, one call each (`_counts.device_stack`); a video with a file that is
+    missing, of another size or not decoded there goes through the loop below, which raises what it raises today."""
     vid = video["video_id"]
     names = [im["file_name"] for im in video["images"]]
     gt_paths = [os.path.join(truth_dir, vid, n) for n in names]
     pred_paths = [os.path.join(submit_dir, "pan_pred", vid, n) for n in names]
+    n = len(gt_frames)
+    g = device_stack(gt_paths, reader, device, rgb=True)
+    p = device_stack(pred_paths, reader, device, rgb=True) if g is not None else None
+    if p is not None and g.shape == p.shape:
+        return video_tables(vid, gt_frames, pred_frames, g[:n] if n else None, p[:n] if n else None, device)
     gt, pred = [], []
     for gp, pp in zip(gt_paths, pred_paths):
         (g, gsize), (p, psize) = _read_rgb(gp), _read_rgb(pp)
         assert gsize == psize, f"Dismatch shape {gsize} and {psize}"
         gt.append(g)
         pred.append(p)
-    n = len(gt_frames)
     return video_tables(vid, gt_frames, pred_frames, np.stack(gt[:n]) if n else None, np.stack(pred[:n]) if n else None, device)
 
 
@@ -437,15 +444,18 @@ def _collect(gt_jsons, pred_jsons, tables_of):
     return videos, missing
 
 
-def evaluate_vps_files(submit_dir, truth_dir, pan_gt_json_file, device=None, output_dir=None):
+def evaluate_vps_files(submit_dir, truth_dir, pan_gt_json_file, device=None, output_dir=None, reader="host"):
     """`VPSEvaluator.evaluate_vpq` + `evaluate_stq` on a result directory (`pred.json`, `pan_pred/<video>/<frame>.png`): reads every PNG
     once, counts the pair tables of a video with one `pair_counts` call on `device` (default: the GPU when there is one), writes the
-    reference's result files into `output_dir` (default: `submit_dir`) and returns `score_tables`' dict."""
+    reference's result files into `output_dir` (default: `submit_dir`) and returns `score_tables`' dict.  reader "gpu": the PNGs are
+    decoded on the device instead of by Pillow."""
+    check_reader(reader)
     with open(os.path.join(submit_dir, "pred.json")) as f:
         pred_jsons = json.load(f)
     with open(pan_gt_json_file) as f:
         gt_jsons = json.load(f)
-    videos, missing = _collect(gt_jsons, pred_jsons, lambda video, g, p: _tables_from_files(video, g, p, submit_dir, truth_dir, device))
+    videos, missing = _collect(gt_jsons, pred_jsons, lambda video, g, p: _tables_from_files(video, g, p, submit_dir, truth_dir, device,
+                                                                                             reader))
     return _score_or_raise(videos, missing, gt_jsons, output_dir or submit_dir)
 
 
@@ -472,10 +482,11 @@ class VPSEvaluator:
     video's ground-truth PNGs are there it also counts the video's pair tables at once, from the int32 `pred_masks` it was handed: the
     table's columns are moved from segment ids to the colour ids of the record it just wrote.  `evaluate` then reads no predicted PNG."""
 
-    def __init__(self, categories, pan_gt_json_file, truth_dir, output_dir, device=None, png="host"):
+    def __init__(self, categories, pan_gt_json_file, truth_dir, output_dir, device=None, png="host", reader="host"):
         self.categories, self.pan_gt_json_file, self.truth_dir, self._output_dir, self.device = categories, pan_gt_json_file, truth_dir, output_dir, device
         self._gt_jsons = None
         self.png = png                                               # ("host" | "gpu": who compresses the PNGs, results.py)
+        self.reader = check_reader(reader)                           # ("host" | "gpu": who decodes them, _counts.device_stack)
         self.reset()
 
     def _gt(self):
@@ -512,14 +523,15 @@ class VPSEvaluator:
             return None
         pan = outputs["pred_masks"]
         pan = pan if isinstance(pan, torch.Tensor) else torch.as_tensor(np.asarray(pan))
-        gt = _read_stack(gt_paths)
+        gt = device_stack(gt_paths, self.reader, self.device, rgb=True)
+        gt = _read_stack(gt_paths) if gt is None else gt
         if tuple(gt.shape[:3]) != tuple(pan.shape):
             return None                                              # (evaluate() raises the reference's size assertion from the files)
         seg_ids = np.array(sorted({VOID} | {int(s["id"]) for s in outputs["segments_infos"]}), dtype=np.int64)
         gt_ids = id_table(gt_frames)
         device = torch.device(self.device) if self.device is not None else (pan.device if pan.is_cuda else torch.device(
             "cuda" if torch.cuda.is_available() else "cpu"))
-        counts, unknown = pair_counts(torch.from_numpy(gt).to(device), pan.to(device=device, dtype=torch.int32),
+        counts, unknown = pair_counts(torch.as_tensor(gt).to(device), pan.to(device=device, dtype=torch.int32),
                                       torch.from_numpy(gt_ids), torch.from_numpy(seg_ids))
         counts, unknown = counts.cpu().numpy().astype(np.int64), unknown.cpu().numpy().astype(np.int64)
         # segment id -> colour id: the record lists, per frame, the segments that have pixels there, in `segments_infos`' order
@@ -553,7 +565,7 @@ class VPSEvaluator:
 
         def tables_of(video, g, p):
             t = self._tables.get(video["video_id"])
-            return t if t is not None else _tables_from_files(video, g, p, self._output_dir, self.truth_dir, self.device)
+            return t if t is not None else _tables_from_files(video, g, p, self._output_dir, self.truth_dir, self.device, self.reader)
         videos, missing = _collect(gt_jsons, {"annotations": self._predictions}, tables_of)
         return _score_or_raise(videos, missing, gt_jsons, self._output_dir)
 
@@ -564,8 +576,9 @@ def main(argv=None):
     ap.add_argument("--truth_dir", default="datasets/vipseg/VIPSeg_720P/panomasksRGB", help="<truth_dir>/<video>/<frame>.png")
     ap.add_argument("--pan_gt_json_file", default="datasets/vipseg/VIPSeg_720P/panoptic_gt_VIPSeg_val.json")
     ap.add_argument("--device", default=None, help="cuda / cpu (default: the GPU when there is one)")
+    ap.add_argument("--reader", default="host", choices=("host", "gpu"), help="who decodes the PNGs: Pillow on the host, or the device")
     a = ap.parse_args(argv)
-    r = evaluate_vps_files(a.submit_dir, a.truth_dir, a.pan_gt_json_file, a.device)
+    r = evaluate_vps_files(a.submit_dir, a.truth_dir, a.pan_gt_json_file, a.device, reader=a.reader)
     print(r["files"]["vpq-final.txt"], end="")
     print("STQ : {}\nAQ :{}\nIoU:{}".format(r["stq"]["STQ"], r["stq"]["AQ"], r["stq"]["IoU"]))
     return r

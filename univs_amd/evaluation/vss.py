@@ -25,7 +25,7 @@ import warnings
 import numpy as np
 import torch
 
-from ._counts import pick_device as _device, read_png as _read
+from ._counts import check_reader, device_stack, pick_device as _device, read_png as _read, stack as _stack
 from .vss_counts import CLIP_NUMS, vss_counts
 
 
@@ -125,7 +125,7 @@ def video_counts(name, entries, frames, num_classes, device=None):
     windows = None
     plain = sorted((f for f in frames if f[0][0] != "."), key=lambda f: f[0])
     if plain:
-        c, windows = _count(np.stack([f[1] for f in plain]), np.stack([f[2] for f in plain]), num_classes, device)
+        c, windows = _count(_stack([f[1] for f in plain]), _stack([f[2] for f in plain]), num_classes, device)
         confusion += c
     for f in frames:
         if f[0][0] == ".":
@@ -137,12 +137,17 @@ def video_counts(name, entries, frames, num_classes, device=None):
     return VideoCounts(name, entries, confusion, windows)
 
 
-def _counts_from_files(video, submit_dir, data_dir, num_classes, device):
+def _counts_from_files(video, submit_dir, data_dir, num_classes, device, reader="host"):
     """One video read as `evaluate_miou` reads it (vss_evaluation.py:140-159): the mask directory's entries in listing order, the ground
     truth before the prediction, the size assertion per file.  When a file fails, the files before it are counted first: the reference
-    would have met their ValueError earlier."""
+    would have met their ValueError earlier.  reader "gpu": the two sides are decoded on the device, one call each; a video with a
+    file that is missing, of another size or not decoded there goes through the loop below."""
     mask_dir = os.path.join(data_dir, "data", video, "mask")
     listing = os.listdir(mask_dir)
+    g = device_stack([os.path.join(mask_dir, tar) for tar in listing], reader, device)
+    p = device_stack([os.path.join(submit_dir, video, tar) for tar in listing], reader, device) if g is not None else None
+    if p is not None and g.shape == p.shape:
+        return video_counts(video, len(listing), [(tar, g[i], p[i]) for i, tar in enumerate(listing)], num_classes, device)
     frames, failure = [], None
     for tar in listing:
         try:
@@ -160,16 +165,18 @@ def _counts_from_files(video, submit_dir, data_dir, num_classes, device):
     return video_counts(video, len(listing), frames, num_classes, device)
 
 
-def evaluate_vss_files(submit_dir, data_dir, split_file="val.txt", num_classes=124, device=None, output_dir=None):
+def evaluate_vss_files(submit_dir, data_dir, split_file="val.txt", num_classes=124, device=None, output_dir=None, reader="host"):
     """`VSSEvaluator.evaluate` (and the two scripts) on a VSPW tree: the videos of `data_dir/split_file`, the ground truth in
     `data_dir/data/<video>/mask/*.png`, the predictions in `submit_dir/<video>/<name>.png`.  Every PNG is read once into one uint8 stack
     per side and video, counted by one `vss_counts` call on `device` (default: the GPU when there is one).  Writes miou-final.txt,
     vc8-final.txt and vc16-final.txt into `output_dir` (default: `submit_dir`, as the scripts) and returns `score_counts`' dict.
+    reader "gpu": the PNGs are decoded on the device (`_counts.device_stack`) instead of by Pillow.
 
     Errors as the reference's, mIoU first: a prediction of another size is an AssertionError, a missing one a FileNotFoundError, a
     confusion cell beyond num_classes^2 a ValueError.  Split lines: see `read_split`."""
     device = _device(device)
-    videos = [_counts_from_files(v, submit_dir, data_dir, num_classes, device) for v in read_split(data_dir, split_file)]
+    check_reader(reader)
+    videos = [_counts_from_files(v, submit_dir, data_dir, num_classes, device, reader) for v in read_split(data_dir, split_file)]
     return score_counts(videos, split_file, submit_dir if output_dir is None else output_dir, num_classes)
 
 
@@ -182,12 +189,14 @@ class VSSEvaluator:
     in the video's mask directory, it also counts the video at once from the tensor it was handed and the ground-truth masks; `evaluate`
     then reads no PNG of that video.  Any other video of the split is scored from the files."""
 
-    def __init__(self, contiguous_id_to_dataset_id, ignore_val, num_classes, data_dir, split_file, output_dir, device=None, eval_miou_res=-1, png="host"):
+    def __init__(self, contiguous_id_to_dataset_id, ignore_val, num_classes, data_dir, split_file, output_dir, device=None, eval_miou_res=-1, png="host",
+                 reader="host"):
         if eval_miou_res > 0:
             raise NotImplementedError("eval_miou_res > 0 rescales the ground truth with mmcv, which the reference's evaluator does not import")
         self.contiguous_id_to_dataset_id, self.ignore_val, self.num_classes = dict(contiguous_id_to_dataset_id), ignore_val, int(num_classes)
         self.data_dir, self.split_file, self._output_dir, self.device = data_dir, split_file, output_dir, device
         self.png = png                                               # ("host" | "gpu": who compresses the PNGs, results.py)
+        self.reader = check_reader(reader)                           # ("host" | "gpu": who decodes them, _counts.device_stack)
         self.reset()
 
     def reset(self):
@@ -224,13 +233,18 @@ class VSSEvaluator:
         sem = outputs["pred_masks"]
         sem = sem if isinstance(sem, torch.Tensor) else torch.as_tensor(np.asarray(sem))
         order = sorted(range(len(names)), key=lambda i: names[i])
-        gt = [_read(os.path.join(mask_dir, names[i])) for i in order]
-        if any(g.ndim != 2 or g.dtype != np.uint8 or tuple(g.shape) != tuple(sem.shape[1:]) for g in gt):
-            return None                                              # (evaluate() raises the reference's size assertion from the files)
         device = _device(self.device, sem)
+        gt = device_stack([os.path.join(mask_dir, names[i]) for i in order], self.reader, device)
+        if gt is None:
+            gt = [_read(os.path.join(mask_dir, names[i])) for i in order]
+            if any(g.ndim != 2 or g.dtype != np.uint8 or tuple(g.shape) != tuple(sem.shape[1:]) for g in gt):
+                return None                                          # (evaluate() raises the reference's size assertion from the files)
+            gt = np.stack(gt)
+        elif tuple(gt.shape[1:]) != tuple(sem.shape[1:]):
+            return None
         pred = self._png_bytes(sem, device)[torch.as_tensor(order, device=device)]
         try:
-            confusion, windows = _count(np.stack(gt), pred, self.num_classes, device)
+            confusion, windows = _count(gt, pred, self.num_classes, device)
         except ValueError:
             return None                                              # (raised by evaluate(), from the files, in the split's order)
         return VideoCounts(video, len(listing), confusion, windows)
@@ -241,7 +255,7 @@ class VSSEvaluator:
         videos = []
         for v in read_split(self.data_dir, self.split_file):
             c = self._counts.get(v)
-            videos.append(c if c is not None else _counts_from_files(v, self._output_dir, self.data_dir, self.num_classes, device))
+            videos.append(c if c is not None else _counts_from_files(v, self._output_dir, self.data_dir, self.num_classes, device, self.reader))
         return score_counts(videos, self.split_file, "/".join(self._output_dir.split("/")[:-1]), self.num_classes)
 
 
@@ -252,8 +266,9 @@ def main(argv=None):
     ap.add_argument("--split_file", default="val.txt", help="val.txt or test.txt")
     ap.add_argument("--num_classes", type=int, default=124)
     ap.add_argument("--device", default=None, help="cuda / cpu (default: the GPU when there is one)")
+    ap.add_argument("--reader", default="host", choices=("host", "gpu"), help="who decodes the PNGs: Pillow on the host, or the device")
     a = ap.parse_args(argv)
-    r = evaluate_vss_files(a.submit_dir, a.data_dir, a.split_file, a.num_classes, a.device)
+    r = evaluate_vss_files(a.submit_dir, a.data_dir, a.split_file, a.num_classes, a.device, reader=a.reader)
     for text in r["files"].values():
         print(text)
     return r

@@ -1,7 +1,7 @@
 """`python -m univs_amd.run`: a checkpoint and frames on disk to result files.
 
     python -m univs_amd.run --config-file F --weights W (--json J --image-root R --dataset-name N | --video-dir D) --output-dir O
-                            [--resize gpu|host] [--png host|gpu]
+                            [--resize gpu|host] [--png host|gpu] [--reader host|gpu]
                             [--gt-json G [--hota] | --pan-gt-json P --truth-dir T | --davis-root V | --pvos-data V]
                             [KEY VALUE ...]
 
@@ -20,6 +20,8 @@ written.
 
 --png gpu has the result PNGs (the VOS id maps, the VPS panoptic maps) compressed on the device by csrc/png_deflate.hip instead of by
 Pillow on a host core: the same paths and the same pixels, mode and palette, other (larger) files; the default is host.
+--reader gpu has the VPS, DAVIS and VIPOSeg evaluators decode the PNGs they score on the device (csrc/png_inflate.hip) instead of with
+Pillow: the same numbers; the default is host.
 """
 import argparse
 import json
@@ -46,6 +48,7 @@ def parse_args(argv=None):
     ap.add_argument("--output-dir", required=True)
     ap.add_argument("--resize", choices=("gpu", "host"), default="gpu")
     ap.add_argument("--png", choices=("host", "gpu"), default="host", help="who compresses the result PNGs: Pillow, or the HIP encoder")
+    ap.add_argument("--reader", choices=("host", "gpu"), default="host", help="who decodes the PNGs the evaluators score: Pillow, or the HIP decoder")
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--gt-json", help="YouTube-VIS annotation file: score with YTVISEvaluator")
     ap.add_argument("--hota", action="store_true", help="with --gt-json: score with HOTAEvaluator instead of YTVISEvaluator")
@@ -88,16 +91,18 @@ def build_evaluator(args):
         with open(args.pan_gt_json) as f:
             categories = {c["id"]: c for c in json.load(f)["categories"]}
         return VPSEvaluator(categories, args.pan_gt_json, args.truth_dir, args.output_dir, device=args.device,
-                            png=getattr(args, "png", "host"))
+                            png=getattr(args, "png", "host"), reader=getattr(args, "reader", "host"))
     # the two VOS evaluators read <their output_dir>/Annotations: the "inference" folder `write_vos_pngs` writes into
     if getattr(args, "davis_root", None):
         from .evaluation.davis import DAVISEvaluator      # (it takes the image root and drops two components: give them back)
         return DAVISEvaluator(args.dataset_name, os.path.join(args.davis_root, "JPEGImages", "Full-Resolution"),
-                              output_dir=os.path.join(args.output_dir, "inference"), device=args.device)
+                              output_dir=os.path.join(args.output_dir, "inference"), device=args.device,
+                              reader=getattr(args, "reader", "host"))
     if getattr(args, "pvos_data", None):
         from .evaluation.pvos import PVOSEvaluator         # (likewise, one component)
         return PVOSEvaluator(args.dataset_name, os.path.join(args.pvos_data, "JPEGImages"), distributed=False,
-                             output_dir=os.path.join(args.output_dir, "inference"), device=args.device)
+                             output_dir=os.path.join(args.output_dir, "inference"), device=args.device,
+                             reader=getattr(args, "reader", "host"))
     return None
 
 
