@@ -10,6 +10,7 @@
 #include "../../include/univs_frames_hip.h"
 #include "../../include/univs_fused_hip.h"
 #include "../../include/univs_hota_hip.h"
+#include "../../include/univs_jpeg_hip.h"
 #include "../../include/univs_png_hip.h"
 #include "../../include/univs_pngread_hip.h"
 #include "../../include/univs_prompts_hip.h"
@@ -993,6 +994,21 @@ int univs_png_read(const uint8_t* streams, const long long* stream_offsets, cons
   return e.covered(png_read(streams, stream_offsets, desc, palettes, P, filt_offsets, out_offsets, N, streams_total, filt_total, out_total,
                             max_rowbytes, filtered, out, status, e.st),
                    "not covered (max_rowbytes <= 24576, streams_total, filt_total and out_total < 2^31)");
+}
+
+// (include/univs_jpeg_hip.h)
+int univs_jpeg_decode(const uint8_t* src, const long long* src_off, const int* ri, const uint8_t* huff, const uint16_t* quant, int N, int W,
+                      int H, int ncomp, int h, int v, int subseq_bits, int max_intervals, long long src_total, int phases, uint8_t* comp,
+                      int* ivl, int16_t* blocks, uint8_t* planes, uint8_t* out, int* status, int* rounds, void* stream) {
+  const Entry e("univs_jpeg_decode", stream);
+  if (N < 0 || src_total < 0 || max_intervals < 1 || phases < 1 || phases > 3)
+    return e.invalid("bad arguments N=%d src_total=%lld max_intervals=%d phases=%d", N, src_total, max_intervals, phases);
+  if (N == 0) return UNIVS_OK;
+  if (!src || !src_off || !ri || !huff || !quant || !comp || !ivl || !blocks || !planes || !out || !status || !rounds) return e.null_pointer();
+  return e.covered(jpeg_decode(src, src_off, ri, huff, quant, N, W, H, ncomp, h, v, subseq_bits, max_intervals, src_total, phases, comp, ivl,
+                               blocks, planes, out, status, rounds, e.st),
+                   "not covered (16 <= W, H <= 16384, (ncomp, h, v) in {(1, 1, 1), (3, 1, 1), (3, 2, 1), (3, 2, 2)}, subseq_bits a multiple of "
+                   "32 in [32, 2^20], max_intervals <= 2^20, src_total and 3 N H W < 2^31, out 4-byte and planes 8-byte aligned)");
 }
 
 // (include/univs_hota_hip.h)

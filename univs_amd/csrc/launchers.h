@@ -245,6 +245,11 @@ int png_read(const unsigned char* streams, const long long* stream_offsets, cons
              const long long* filt_offsets, const long long* out_offsets, int N, long long streams_total, long long filt_total,
              long long out_total, int max_rowbytes, unsigned char* filtered, unsigned char* out, int* status, hipStream_t st);
 
+// ---- jpeg_decode.hip: returns UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the sizes or the sampling are not covered, or the launch's error
+int jpeg_decode(const unsigned char* src, const long long* src_off, const int* ri, const unsigned char* huff, const unsigned short* quant, int N,
+                int W, int H, int ncomp, int h, int v, int subseq_bits, int max_intervals, long long src_total, int phases, unsigned char* comp,
+                int* ivl, short* blocks, unsigned char* planes, unsigned char* out, int* status, int* rounds, hipStream_t st);
+
 // ---- hota_count.hip: return UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the sizes are not covered, or the launch's error
 int hota_counts(const int* inter, const int* gt_area, const int* tr_area, int D, int G, int T, const int* gt_ids, const int* gt_starts,
                 const int* tr_ids, const int* tr_starts, int C, int max_g, int max_p, const double* thr, int A, int* tp_fn_fp, int* matches,

@@ -4,7 +4,10 @@ frame of the record, read, resized by `ResizeShortestEdge(MIN_SIZE_TEST, MAX_SIZ
 resize="host" is the reference's way, `PIL.Image.resize` per frame on the host (what detectron2's `ResizeTransform` calls for uint8
 images); it needs no GPU.  resize="gpu" decodes on the host, uploads the frames of a video in batches and resizes them with
 csrc/frame_resize.hip, which gives Pillow's bytes exactly (tests/test_frame_resize_gpu.py); `image` then stays on the device, where the
-drivers want it.  Sizes the kernel does not cover go through Pillow.
+drivers want it.  Sizes the kernel does not cover go through Pillow.  decode="gpu" (with resize="gpu" only) also decodes on the device:
+the files' compressed bytes go up, csrc/jpeg_decode.hip gives Pillow's pixels for the baseline JPEG files it covers and the decoded batch
+goes straight to the resize, no pixel crosses the bus; any other file is read on the host as before (images.py: decoded_runs).  The
+default is decode="host", and the dictionaries are equal tensor for tensor (tests/test_jpeg_mapper_gpu.py).
 
 Task "sot" (first-frame annotations) has a mapper of its own, `VOSTestMapper` in vos_mapper.py; this one refuses it and says so.
 Not built: raw video files, training -- each raises NotImplementedError and says which."""
@@ -17,7 +20,7 @@ import torch
 from PIL import Image
 
 from ..modeling.language import clean_strings
-from .images import read_image
+from .images import decoded_runs, read_image
 from .resize_rule import shortest_edge_size
 
 _BATCH_BYTES = 256 << 20                                             # decoded frames uploaded and resized per launch
@@ -65,20 +68,24 @@ def _pil_resize(image, newh, neww):
 
 
 class VideoTestMapper:
-    def __init__(self, short, max_size, image_format="RGB", resize="host", device=None, is_train=False):
+    def __init__(self, short, max_size, image_format="RGB", resize="host", device=None, is_train=False, decode="host"):
         if is_train:
             raise NotImplementedError("training: only the test path of the mapper is built (no sampling, no augmentation, no annotations)")
         if resize not in ("gpu", "host"):
             raise ValueError(f"VideoTestMapper: resize={resize!r} (\"gpu\" or \"host\")")
         if image_format not in ("RGB", "BGR"):
             raise ValueError(f"VideoTestMapper: image_format={image_format!r} (\"RGB\" or \"BGR\")")
-        self.short, self.max_size, self.image_format, self.resize = int(short), int(max_size), image_format, resize
+        if decode not in ("gpu", "host"):
+            raise ValueError(f"VideoTestMapper: decode={decode!r} (\"gpu\" or \"host\")")
+        if decode == "gpu" and resize != "gpu":
+            raise ValueError("VideoTestMapper: decode=\"gpu\" hands device frames to the device resize: it needs resize=\"gpu\"")
+        self.short, self.max_size, self.image_format, self.resize, self.decode = int(short), int(max_size), image_format, resize, decode
         self.device = torch.device("cuda" if device is None else device) if resize == "gpu" else None
 
     @classmethod
-    def from_config(cls, cfg, resize="host", device=None):
+    def from_config(cls, cfg, resize="host", device=None, decode="host"):
         short, max_size = resize_params_from_config(cfg)
-        return cls(short, max_size, cfg.INPUT.FORMAT, resize=resize, device=device)
+        return cls(short, max_size, cfg.INPUT.FORMAT, resize=resize, device=device, decode=decode)
 
     # ---- the two ways of resizing: both return the list of uint8 [3, h, w] tensors ------------------------------------------------------
     def _host(self, file_names):
@@ -90,11 +97,15 @@ class VideoTestMapper:
         return images
 
     def _gpu_batch(self, batch):
+        """The resize of a batch of RGB frames of one size: host arrays [H, W, 3] (uploaded here), or one device tensor [n, H, W, 3]."""
         from .. import frames_ops
+        on_device = torch.is_tensor(batch)
         H, W = batch[0].shape[:2]
         out_hw = shortest_edge_size(H, W, self.short, self.max_size)
         bgr = self.image_format == "BGR"
-        out = frames_ops.resize_frames_u8(torch.from_numpy(np.stack(batch)).to(self.device), out_hw, bgr=bgr)
+        out = frames_ops.resize_frames_u8(batch.contiguous() if on_device else torch.from_numpy(np.stack(batch)).to(self.device), out_hw, bgr=bgr)
+        if out is None and on_device:
+            batch = list(batch.cpu().numpy())
         if out is None:                                              # not covered (a down-scale beyond 4): Pillow, then the upload
             if "uncovered" not in _logged:
                 _logged.add("uncovered")
@@ -105,6 +116,8 @@ class VideoTestMapper:
         return list(out)
 
     def _gpu(self, file_names):
+        if self.decode == "gpu":
+            return [im for run in decoded_runs(file_names, self.device, _BATCH_BYTES) for im in self._gpu_batch(run)]
         images, batch = [], []
         for path in file_names:
             image = read_image(path, "RGB")                          # (the kernel's flag reverses the channels for "BGR")

@@ -1,7 +1,7 @@
 """`python -m univs_amd.run`: a checkpoint and frames on disk to result files.
 
     python -m univs_amd.run --config-file F --weights W (--json J --image-root R --dataset-name N | --video-dir D) --output-dir O
-                            [--resize gpu|host] [--png host|gpu] [--reader host|gpu]
+                            [--resize gpu|host] [--decode host|gpu] [--png host|gpu] [--reader host|gpu]
                             [--gt-json G [--hota] | --pan-gt-json P --truth-dir T | --davis-root V | --pvos-data V]
                             [KEY VALUE ...]
 
@@ -22,6 +22,8 @@ written.
 Pillow on a host core: the same paths and the same pixels, mode and palette, other (larger) files; the default is host.
 --reader gpu has the VPS, DAVIS and VIPOSeg evaluators decode the PNGs they score on the device (csrc/png_inflate.hip) instead of with
 Pillow: the same numbers; the default is host.
+--decode gpu (with --resize gpu) has the mappers decode the JPEG frames on the device (csrc/jpeg_decode.hip) instead of with Pillow: the
+same pixels; files the decoder does not cover are read on the host as before; the default is host.
 """
 import argparse
 import json
@@ -47,6 +49,7 @@ def parse_args(argv=None):
     ap.add_argument("--video-dir", help="a folder whose sub-folders hold the frames of one video each")
     ap.add_argument("--output-dir", required=True)
     ap.add_argument("--resize", choices=("gpu", "host"), default="gpu")
+    ap.add_argument("--decode", choices=("host", "gpu"), default="host", help="who decodes the JPEG frames: Pillow, or the HIP decoder (needs --resize gpu)")
     ap.add_argument("--png", choices=("host", "gpu"), default="host", help="who compresses the result PNGs: Pillow, or the HIP encoder")
     ap.add_argument("--reader", choices=("host", "gpu"), default="host", help="who decodes the PNGs the evaluators score: Pillow, or the HIP decoder")
     ap.add_argument("--device", default="cuda")
@@ -140,7 +143,7 @@ def main(argv=None):
         records = load_video_json(args.json, args.image_root, args.dataset_name)
     else:
         records = video_records_from_dir(args.video_dir)
-    mapper = (VOSTestMapper if args.vos else VideoTestMapper).from_config(cfg, resize=args.resize, device=args.device)
+    mapper = (VOSTestMapper if args.vos else VideoTestMapper).from_config(cfg, resize=args.resize, device=args.device, decode=getattr(args, "decode", "host"))
     os.makedirs(args.output_dir, exist_ok=True)
     evaluator = build_evaluator(args)
 
