@@ -11,6 +11,7 @@
 #include "../../include/univs_fused_hip.h"
 #include "../../include/univs_hota_hip.h"
 #include "../../include/univs_jpeg_hip.h"
+#include "../../include/univs_jpegenc_hip.h"
 #include "../../include/univs_png_hip.h"
 #include "../../include/univs_pngread_hip.h"
 #include "../../include/univs_prompts_hip.h"
@@ -1009,6 +1010,22 @@ int univs_jpeg_decode(const uint8_t* src, const long long* src_off, const int* r
                                blocks, planes, out, status, rounds, e.st),
                    "not covered (16 <= W, H <= 16384, (ncomp, h, v) in {(1, 1, 1), (3, 1, 1), (3, 2, 1), (3, 2, 2)}, subseq_bits a multiple of "
                    "32 in [32, 2^20], max_intervals <= 2^20, src_total and 3 N H W < 2^31, out 4-byte and planes 8-byte aligned)");
+}
+
+// (include/univs_jpegenc_hip.h)
+int univs_jpeg_encode(const uint8_t* rgb, const void* ids, int ids_is_i32, const uint8_t* lut, int K, int edge, int N, int H, int W, int h,
+                      int v, int quality, int phases, int16_t* blocks, uint32_t* sizes, long long* bit_off, long long* totals,
+                      const long long* raw_off, long long raw_total, uint8_t* raw, uint8_t* out, long long* out_len, int* status, void* stream) {
+  const Entry e("univs_jpeg_encode", stream);
+  if (N < 0 || phases < 1 || phases > 3 || raw_total < 0 || (ids && (K < 1 || edge < -1 || edge > 0xFFFFFF)))
+    return e.invalid("bad arguments N=%d phases=%d raw_total=%lld ids=%s K=%d edge=%d", N, phases, raw_total, ids ? "given" : "NULL", K, edge);
+  if (N == 0) return UNIVS_OK;
+  if (!rgb || (ids && !lut) || !blocks || !sizes || !bit_off || !totals || !status || ((phases & 2) && (!raw_off || !raw || !out || !out_len)))
+    return e.null_pointer();
+  return e.covered(jpeg_encode(rgb, ids, ids_is_i32, lut, K, edge, N, H, W, h, v, quality, phases, blocks, sizes, bit_off, totals, raw_off,
+                               raw_total, raw, out, out_len, status, e.st),
+                   "not covered (1 <= W, H <= 16384, (h, v) in {(1, 1), (2, 1), (2, 2)}, 1 <= quality <= 100, 3 N H W < 2^31, raw_total < 2^40, "
+                   "blocks 16-byte and raw 4-byte aligned)");
 }
 
 // (include/univs_hota_hip.h)

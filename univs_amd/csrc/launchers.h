@@ -250,6 +250,12 @@ int jpeg_decode(const unsigned char* src, const long long* src_off, const int* r
                 int W, int H, int ncomp, int h, int v, int subseq_bits, int max_intervals, long long src_total, int phases, unsigned char* comp,
                 int* ivl, short* blocks, unsigned char* planes, unsigned char* out, int* status, int* rounds, hipStream_t st);
 
+// ---- jpeg_encode.hip: returns UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the sizes, the sampling or the quality are not covered, or the
+// launch's error
+int jpeg_encode(const unsigned char* rgb, const void* ids, int ids_is_i32, const unsigned char* lut, int K, int edge, int N, int H, int W, int h,
+                int v, int quality, int phases, short* blocks, unsigned* sizes, long long* bit_off, long long* totals, const long long* raw_off,
+                long long raw_total, unsigned char* raw, unsigned char* out, long long* out_len, int* status, hipStream_t st);
+
 // ---- hota_count.hip: return UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the sizes are not covered, or the launch's error
 int hota_counts(const int* inter, const int* gt_area, const int* tr_area, int D, int G, int T, const int* gt_ids, const int* gt_starts,
                 const int* tr_ids, const int* tr_starts, int C, int max_g, int max_p, const double* thr, int A, int* tp_fn_fp, int* matches,

@@ -312,6 +312,55 @@ def write_rvos_pngs(output_dir: str, file_names: Sequence[str], first_frame_idx:
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# Overlay JPEGs: a result drawn over its frames (inference/overlay_rule.py), something a person can look at
+# ------------------------------------------------------------------------------------------------------------------
+def _jpg_name(file_name: str) -> str:
+    return file_name.split("/")[-1].rsplit(".", 1)[0] + ".jpg"
+
+
+def write_overlay_jpegs(output_dir: str, file_names: Sequence[str], first_frame_idx: int, frames, ids, lut, edge=(255, 255, 240),
+                        quality: int = 90, sampling: str = "420", jpeg="host"):
+    """`ids` ([T', H, W] integer id maps, tensor or array) over `frames` (T' uint8 [H, W, 3] arrays or tensors, or one [T', H, W, 3]: the
+    files' own pixels) with the colours and alphas of `lut` (uint8 [K, 4]) -> `<output_dir>/inference/Overlays/<video>/<frame>.jpg`, frame
+    t the file `file_names[first_frame_idx + t]`.  jpeg="host": `overlay_rule` in numpy, then `PIL.Image.save`; jpeg="gpu": the fused entry
+    of csrc/jpeg_encode.hip (jpegenc_ops.encode_jpegs), frames and ids uploaded where they are not on the device yet.  The same files byte
+    for byte.  Returns the paths."""
+    from .overlay_rule import check_lut, overlay_rule
+    if jpeg not in ("host", "gpu"):
+        raise ValueError(f'jpeg="{jpeg}": "host" or "gpu"')
+    lut = check_lut(lut.cpu().numpy() if isinstance(lut, torch.Tensor) else lut)
+    n = len(ids)
+    if len(frames) != n:
+        raise ValueError(f"{len(frames)} frames against {n} id maps")
+    save_dir = os.path.join(output_dir, "inference/Overlays", file_names[0].split("/")[-2])
+    os.makedirs(save_dir, exist_ok=True)
+    paths = [os.path.join(save_dir, _jpg_name(file_names[first_frame_idx + t])) for t in range(n)]
+    if n == 0:
+        return paths
+    if jpeg == "gpu":
+        from .. import jpegenc_ops
+        if isinstance(frames, torch.Tensor):
+            rgb = frames
+        else:
+            rgb = torch.stack([f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f)) for f in frames])
+        rgb = rgb.to(device=rgb.device if rgb.is_cuda else "cuda", dtype=torch.uint8).contiguous()
+        t = ids if isinstance(ids, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ids))
+        files = jpegenc_ops.encode_jpegs(rgb, quality, sampling, ids=t.to(rgb.device), lut=lut, edge=edge)
+        for path, data in zip(paths, files):
+            with open(path, "wb") as f:
+                f.write(data)
+        return paths
+    from PIL import Image
+    ids = ids.cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
+    for path, frame, m in zip(paths, frames, ids):
+        frame = frame.cpu().numpy() if isinstance(frame, torch.Tensor) else np.asarray(frame)
+        img = Image.fromarray(overlay_rule(frame, m, lut, edge))
+        img.save(path, "JPEG", quality=int(quality), subsampling={"444": 0, "422": 1, "420": 2}[sampling])
+        img.close()
+    return paths
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # VPS (VIPSeg) and VSS (VSPW) result files
 # ------------------------------------------------------------------------------------------------------------------
 def rgb2id(color):

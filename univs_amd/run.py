@@ -2,6 +2,7 @@
 
     python -m univs_amd.run --config-file F --weights W (--json J --image-root R --dataset-name N | --video-dir D) --output-dir O
                             [--resize gpu|host] [--decode host|gpu] [--png host|gpu] [--reader host|gpu]
+                            [--visualize off|host|gpu [--categories-json C]]
                             [--gt-json G [--hota] | --pan-gt-json P --truth-dir T | --davis-root V | --pvos-data V]
                             [KEY VALUE ...]
 
@@ -24,6 +25,12 @@ Pillow on a host core: the same paths and the same pixels, mode and palette, oth
 Pillow: the same numbers; the default is host.
 --decode gpu (with --resize gpu) has the mappers decode the JPEG frames on the device (csrc/jpeg_decode.hip) instead of with Pillow: the
 same pixels; files the decoder does not cover are read on the host as before; the default is host.
+--visualize host|gpu writes something a person can look at: per video O/inference/Overlays/<video>/<frame>.jpg, the result drawn over the
+file's own pixels at their original size (inference/overlay_rule.py: the table's colour blended in by its alpha, a contour where the id
+changes), and a legend.json of the ids drawn.  Drawn are the VOS driver's id maps in the video's palette, the `pred_masks` of a VSS or VPS
+output in the category colours (--categories-json, else the default palette) and VIS results that carry per-frame masks; an output without
+a per-pixel result at the output size prints one line and writes nothing.  host draws with numpy and encodes with Pillow, gpu does both
+inside csrc/jpeg_encode.hip: the same files byte for byte; with --decode gpu the frames never leave the device.  The default is off.
 """
 import argparse
 import json
@@ -52,6 +59,9 @@ def parse_args(argv=None):
     ap.add_argument("--decode", choices=("host", "gpu"), default="host", help="who decodes the JPEG frames: Pillow, or the HIP decoder (needs --resize gpu)")
     ap.add_argument("--png", choices=("host", "gpu"), default="host", help="who compresses the result PNGs: Pillow, or the HIP encoder")
     ap.add_argument("--reader", choices=("host", "gpu"), default="host", help="who decodes the PNGs the evaluators score: Pillow, or the HIP decoder")
+    ap.add_argument("--visualize", choices=("off", "host", "gpu"), default="off",
+                    help="write overlay JPEGs of the results: drawn and encoded by numpy and Pillow, or by the HIP encoder")
+    ap.add_argument("--categories-json", help="with --visualize: a file whose \"categories\" ({id, name, color}) colour and name VPS / VSS classes")
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--gt-json", help="YouTube-VIS annotation file: score with YTVISEvaluator")
     ap.add_argument("--hota", action="store_true", help="with --gt-json: score with HOTAEvaluator instead of YTVISEvaluator")
@@ -130,6 +140,87 @@ def write_vos_outputs(output_dir, inputs, outputs, num_frames, clip_stride, png=
     return paths
 
 
+def _legend(lut, names, present):
+    """{row: {"name", "color", "alpha"}} of the rows that are drawn: those that occur in the id maps and are not transparent."""
+    return {str(k): {"name": str(names.get(k, k)), "color": [int(c) for c in lut[k, :3]], "alpha": int(lut[k, 3])}
+            for k in sorted(present) if lut[k, 3] > 0}
+
+
+def _category_table(args, alpha, n_default):
+    """(lut, {row: name}, {category id: row}) from --categories-json ({"categories": [{"id", "name", "color"}]}), or without one the
+    default palette with row = id + 1."""
+    from .inference import overlay_rule as ov
+    if getattr(args, "categories_json", None):
+        with open(args.categories_json) as f:
+            cats = {int(c["id"]): c for c in json.load(f)["categories"]}
+        lut, order = ov.lut_from_categories(cats, alpha)
+        return lut, {row: cats[cid].get("name", cid) for row, cid in enumerate(order) if cid is not None}, {cid: row for row, cid in enumerate(order)}
+    lut = ov.lut_from_palette(ov.default_palette(n_default + 1), alpha)
+    return lut, {}, None
+
+
+def overlay_tables(args, inputs, outputs):
+    """[(first frame, id maps [T', H, W], lut, {row: name})] of one video's output, or a sentence saying why it holds nothing to draw:
+    the VOS driver's per-clip id maps with the video's palette; a VSS or VPS output's `pred_masks` with the category colours; VIS
+    results that carry per-frame masks, through `idmap_from_instances`."""
+    from .inference import overlay_rule as ov
+    video = inputs[0]
+    if args.vos:
+        vos = args.vos_schedule
+        pal = video.get("mask_palette")
+        lut = ov.lut_from_palette(pal if pal is not None else ov.default_palette())
+        return [(first, m, lut, {}) for first, m in zip(vos_clip_offsets(len(outputs), *vos), outputs)]
+    if isinstance(outputs, dict) and outputs.get("task") == "vss" and "pred_masks" in outputs:
+        sem = torch.as_tensor(outputs["pred_masks"])
+        lut, names, rows = _category_table(args, ov.ALPHA_VSS, int(sem.max()) + 1 if sem.numel() else 1)
+        return [(0, sem + 1, lut, names)]                             # contiguous class c: row c + 1 (row 0 is "nothing", transparent)
+    if isinstance(outputs, dict) and outputs.get("task") == "vps" and "pred_masks" in outputs:
+        pan = torch.as_tensor(outputs["pred_masks"]).long()
+        infos = outputs["segments_infos"]
+        lut, names, rows = _category_table(args, ov.ALPHA_VPS, max([int(i["category_id"]) for i in infos], default=0))
+        ids = torch.zeros_like(pan, dtype=torch.int32)
+        for info in infos:                                           # a segment is drawn in its category's colour
+            row = rows.get(int(info["category_id"]), 0) if rows is not None else int(info["category_id"])
+            ids[pan == int(info["id"])] = row
+        return [(0, ids, lut, names)]
+    if isinstance(outputs, list) and outputs and all(isinstance(c, list) and all(isinstance(r, dict) and "masks" in r for r in c) for c in outputs):
+        tables = []
+        for clip in outputs:
+            if not clip:
+                continue
+            masks = torch.stack([torch.as_tensor(r["masks"]) for r in clip])
+            scores = torch.stack([torch.as_tensor(r["score"]).float().max() for r in clip])
+            lut = ov.lut_from_palette(ov.default_palette(len(clip) + 1))
+            tables.append((int(clip[0]["frame_id_start"]), ov.idmap_from_instances(masks, scores), lut,
+                           {k + 1: "object %d" % r["obj_id"] for k, r in enumerate(clip)}))
+        return tables
+    return "the output holds no per-pixel result at the output size"
+
+
+def write_overlays(args, inputs, outputs):
+    """--visualize: the overlays of one video (`results.write_overlay_jpegs`) and its legend.json; the frames are read again at their
+    original size, on the device with --decode gpu.  Returns the paths."""
+    from .data import read_images
+    from .inference.results import write_overlay_jpegs
+    video = inputs[0]
+    tables = overlay_tables(args, inputs, outputs)
+    if isinstance(tables, str):
+        print(f"--visualize: video {video.get('video_id')}: {tables}; nothing written")
+        return []
+    names = video["file_names"]
+    frames = read_images(names, decode=args.decode, device=args.device if args.decode == "gpu" else None)
+    paths, legend = [], {}
+    for first, ids, lut, row_names in tables:
+        n = min(len(ids), len(names) - first)
+        paths += write_overlay_jpegs(args.output_dir, names, first, frames[first:first + n], ids[:n], lut, jpeg=args.visualize)
+        present = torch.unique(torch.as_tensor(ids[:n]).long().clamp(0, len(lut) - 1)).tolist()
+        legend.update(_legend(lut, row_names, present))
+    if paths:
+        with open(os.path.join(os.path.dirname(paths[0]), "legend.json"), "w") as f:
+            json.dump(legend, f, indent=1, sort_keys=True)
+    return paths
+
+
 def main(argv=None):
     args = parse_args(argv)
     cfg = load_cfg(args.config_file, args.opts)
@@ -155,6 +246,15 @@ def main(argv=None):
         write_vos_outputs(args.output_dir, inputs, outputs, vos.num_frames, vos.clip_stride, png=args.png)
 
     on_output = save_vos if args.vos else (None if evaluator is not None else save)
+    if args.visualize != "off":
+        if args.vos:
+            args.vos_schedule = (model.inference_video_vos.num_frames, model.inference_video_vos.clip_stride)
+        keep = on_output
+
+        def on_output(inputs, outputs):
+            if keep is not None:
+                keep(inputs, outputs)
+            write_overlays(args, inputs, outputs)
     results = inference_on_videos(model, records, mapper, evaluator, on_output=on_output)
     if evaluator is not None:
         print(json.dumps(results, default=str))
