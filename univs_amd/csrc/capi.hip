@@ -10,6 +10,7 @@
 #include "../../include/univs_frames_hip.h"
 #include "../../include/univs_fused_hip.h"
 #include "../../include/univs_hota_hip.h"
+#include "../../include/univs_idmap_hip.h"
 #include "../../include/univs_jpeg_hip.h"
 #include "../../include/univs_jpegenc_hip.h"
 #include "../../include/univs_png_hip.h"
@@ -967,6 +968,26 @@ int univs_resize_rle_masks_u8(const int32_t* bounds, const int32_t* starts, long
   if (!bounds || !starts || !ty || !tx || !masks || !boxes) return e.null_pointer();
   return e.covered(resize_rle_masks_u8(bounds, starts, n_bounds, N, H, W, ty, tx, Ho, Wo, masks, boxes, e.st),
                    "not covered (H W < 2^31, n_bounds < 2^31, N Ho Wo < 2^31)");
+}
+
+// (include/univs_idmap_hip.h)
+int univs_idmap_census_u8(const uint8_t* ids, int F, int H, int W, int32_t* count, int32_t* box, void* stream) {
+  const Entry e("univs_idmap_census_u8", stream);
+  if (F < 0 || H < 1 || W < 1) return e.invalid("bad arguments F=%d H=%d W=%d", F, H, W);
+  if (F == 0) return UNIVS_OK;
+  if (!ids || !count || !box) return e.null_pointer();
+  return e.covered(idmap_census_u8(ids, F, H, W, count, box, e.st), "not covered (F H W < 2^31)");
+}
+
+int univs_idmap_prompts_u8(const uint8_t* ids, int F, int H, int W, const int32_t* frame, const int32_t* value, int N, const int32_t* ty,
+                           const int32_t* tx, int Ho, int Wo, uint8_t* masks, int32_t* boxes, void* stream) {
+  const Entry e("univs_idmap_prompts_u8", stream);
+  if (N < 0 || F < 0 || (N > 0 && F == 0) || H < 1 || W < 1 || Ho < 1 || Wo < 1)
+    return e.invalid("bad arguments F=%d H=%d W=%d N=%d Ho=%d Wo=%d", F, H, W, N, Ho, Wo);
+  if (N == 0) return UNIVS_OK;
+  if (!ids || !frame || !value || !ty || !tx || !masks || !boxes) return e.null_pointer();
+  return e.covered(idmap_prompts_u8(ids, F, H, W, frame, value, N, ty, tx, Ho, Wo, masks, boxes, e.st),
+                   "not covered (F H W < 2^31, N Ho Wo < 2^31)");
 }
 
 // (include/univs_png_hip.h)

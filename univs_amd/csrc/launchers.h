@@ -236,6 +236,11 @@ int resize_frames_u8(const unsigned char* src, int T, int Hi, int Wi, int Ho, in
 int resize_rle_masks_u8(const int* bounds, const int* starts, long long n_bounds, int N, int H, int W, const int* ty, const int* tx, int Ho,
                         int Wo, unsigned char* masks, int* boxes, hipStream_t st);
 
+// ---- idmap_prompts.hip: return UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the sizes are not covered, or the launch's error
+int idmap_census_u8(const unsigned char* ids, int F, int H, int W, int* count, int* box, hipStream_t st);
+int idmap_prompts_u8(const unsigned char* ids, int F, int H, int W, const int* frame, const int* value, int N, const int* ty, const int* tx,
+                     int Ho, int Wo, unsigned char* masks, int* boxes, hipStream_t st);
+
 // ---- png_deflate.hip: returns UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the sizes are not covered, or the launch's error
 int png_deflate_maps(const void* src, int src_is_i32, int N, int H, int W, const unsigned char* lut, int K, int C, int rows_per_stripe,
                      unsigned char* scratch, unsigned char* out, long long* offsets, hipStream_t st);

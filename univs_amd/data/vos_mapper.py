@@ -13,6 +13,13 @@ resize="host" is that, with Pillow itself; it needs no GPU.  resize="gpu" reads 
 video at once (`runs_from_rles`), uploads them in one copy and resizes them in one call of csrc/mask_prompt_resize.hip, which also
 gives the boxes: no source-resolution plane exists, masks and boxes stay on the device.  Both give identical tensors
 (tests/test_prompt_masks_gpu.py).  Sizes the kernel does not cover, and videos whose annotated frames differ in size, go the host way.
+
+The records of `vos_records_from_dirs` (vos_folders.py) give an object as `{"png": path, "value": v}` instead of a `"segmentation"`:
+its plane is (the annotation PNG's id map == v).  resize="host" opens the PNG by the converter's expression, compares and resizes that
+plane with Pillow.  resize="gpu" loads the id maps of the annotated frames once -- one upload, or with decode="gpu" decoded on the
+device by png_read_ops.read_pngs_device -- and gathers all objects' masks and boxes from them in one call of csrc/idmap_prompts.hip: NEAREST
+is a gather, so neither planes nor codes exist.  Same tensors from all of them (tests/test_vos_folders_gpu.py), same fall-backs.
+`mask_palette` is then the palette of the record's first annotation PNG, which is `get_palette`'s answer in that layout.
 """
 import logging
 
@@ -24,6 +31,7 @@ from ..evaluation.vis_counts import runs_from_rles
 from ..inference.results import rle_decode
 from ..inference.video_vos import FrameAnnotations
 from .mapper import VideoTestMapper, _logged, get_palette
+from .vos_folders import read_idmap
 
 
 def bitmask_boxes(masks):
@@ -40,9 +48,22 @@ def bitmask_boxes(masks):
 class VOSTestMapper(VideoTestMapper):
     """`VideoTestMapper` for the records of `load_vos_json`: same constructor and `from_config`."""
 
-    def _host_masks(self, objs, out_hw):
+    def _idmap(self, path, dataset_name):
+        """The id map of an annotation PNG, read once per video."""
+        cache = self.__dict__.setdefault("_idmaps", {})
+        if path not in cache:
+            cache[path] = read_idmap(path, dataset_name)
+        return cache[path]
+
+    def _source_plane(self, o, dataset_name):
+        """uint8 [H, W] of 0 / 1: the decoded run-length code of a json record's object, (id map == value) of a folder record's."""
+        if "png" in o:
+            return (self._idmap(o["png"], dataset_name) == o["value"]).astype(np.uint8)
+        return rle_decode(o["segmentation"])
+
+    def _host_masks(self, objs, out_hw, dataset_name=""):
         newh, neww = out_hw
-        planes = [np.asarray(Image.fromarray(rle_decode(o["segmentation"])).resize((neww, newh), Image.NEAREST)) for o in objs]
+        planes = [np.asarray(Image.fromarray(self._source_plane(o, dataset_name)).resize((neww, newh), Image.NEAREST)) for o in objs]
         masks = torch.from_numpy(np.stack(planes)).bool()
         return masks, bitmask_boxes(masks)
 
@@ -62,7 +83,42 @@ class VOSTestMapper(VideoTestMapper):
         ends = np.cumsum([len(objs) for objs in frames]).tolist()
         return [(masks[b - len(objs):b], boxes[b - len(objs):b]) for objs, b in zip(frames, ends)]
 
+    def _gpu_idmap_masks(self, frames, in_hw, out_hw, video_id, dataset_name=""):
+        """`_gpu_masks` for folder records: the id maps of the annotated frames go up once (or are decoded on the device), one call of
+        csrc/idmap_prompts.hip gives every object's mask and box; None where the kernel does not cover the sizes, the id maps differ
+        in size, or a frame's objects name more than one PNG out of order."""
+        from .. import idmap_ops
+        paths, frame, value = [], [], []
+        for objs in frames:
+            for o in objs:
+                if o["png"] not in paths:
+                    paths.append(o["png"])
+                frame.append(paths.index(o["png"]))
+                value.append(int(o["value"]))
+        if any(a > b for a, b in zip(frame, frame[1:])):
+            return None
+        if self.decode == "gpu":
+            from .vos_folders import _device_maps
+            maps = _device_maps(paths, dataset_name, self.device)
+            if len({tuple(m.shape) for m in maps}) != 1 or maps[0].dim() != 2:
+                return None
+            ids = torch.stack(maps)
+            lists = torch.tensor([frame, value], dtype=torch.int32).to(self.device)
+            frame_d, value_d = lists[0], lists[1]
+        else:
+            maps = [self._idmap(p, dataset_name) for p in paths]
+            if len({m.shape for m in maps}) != 1 or maps[0].ndim != 2:
+                return None
+            ids, frame_d, value_d = idmap_ops.upload_prompts(np.stack(maps), frame, value, self.device)   # one upload
+        out = idmap_ops.idmap_prompts_u8(ids, frame_d, value_d, out_hw)
+        if out is None:
+            return None
+        masks, boxes = out[0].view(torch.bool), out[1].to(torch.float32)
+        ends = np.cumsum([len(objs) for objs in frames]).tolist()
+        return [(masks[b - len(objs):b], boxes[b - len(objs):b]) for objs, b in zip(frames, ends)]
+
     def __call__(self, record):
+        self._idmaps = {}
         if record["task"] != "sot":
             raise ValueError(f"VOSTestMapper: a record of task {record['task']!r}; data.VideoTestMapper maps the other tasks")
         d = self._map(record)
@@ -71,10 +127,14 @@ class VOSTestMapper(VideoTestMapper):
         kept = {f: [o for o in objs if o.get("iscrowd", 0) == 0] for f, objs in enumerate(annotations)}
         kept = {f: objs for f, objs in kept.items() if objs}
         sizes = {f: tuple(d["image"][f].shape[1:]) for f in kept}
+        from_folders = bool(kept) and all("png" in o for objs in kept.values() for o in objs)
         on_gpu = None
         if self.resize == "gpu" and kept:
             if len(set(sizes.values())) == 1:
-                on_gpu = self._gpu_masks(list(kept.values()), in_hw, next(iter(sizes.values())), d.get("video_id"))
+                if from_folders:
+                    on_gpu = self._gpu_idmap_masks(list(kept.values()), in_hw, next(iter(sizes.values())), d.get("video_id"), d["dataset_name"])
+                else:
+                    on_gpu = self._gpu_masks(list(kept.values()), in_hw, next(iter(sizes.values())), d.get("video_id"))
                 on_gpu = on_gpu and dict(zip(kept, on_gpu))
             if on_gpu is None and "vos-uncovered" not in _logged:
                 _logged.add("vos-uncovered")
@@ -89,11 +149,16 @@ class VOSTestMapper(VideoTestMapper):
             if on_gpu is not None:
                 masks, boxes = on_gpu[f]
             else:
-                masks, boxes = self._host_masks(objs, size)
+                masks, boxes = self._host_masks(objs, size, d["dataset_name"])
                 if self.resize == "gpu":
                     masks, boxes = masks.to(self.device), boxes.to(self.device)
             classes = torch.as_tensor([int(o["category_id"]) for o in objs], dtype=torch.int64, device=masks.device)
             ori_ids = [int(o["ori_id"]) if "ori_id" in o else int(o["id"]) for o in objs]
             d["instances"].append(FrameAnnotations(size, ori_ids, masks, boxes, classes))
-        d["mask_palette"] = get_palette(d["file_names"])
+        if record.get("mask_files"):                                 # (a folder record: what get_palette finds in that layout)
+            with Image.open(record["mask_files"][0]) as im:
+                d["mask_palette"] = im.convert("P").getpalette()
+        else:
+            d["mask_palette"] = get_palette(d["file_names"])
+        self._idmaps = {}
         return d

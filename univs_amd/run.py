@@ -1,6 +1,7 @@
 """`python -m univs_amd.run`: a checkpoint and frames on disk to result files.
 
     python -m univs_amd.run --config-file F --weights W (--json J --image-root R --dataset-name N | --video-dir D) --output-dir O
+                            [--masks-dir A --dataset-name N [--vos-meta M]]
                             [--resize gpu|host] [--decode host|gpu] [--png host|gpu] [--reader host|gpu]
                             [--visualize off|host|gpu [--categories-json C]]
                             [--gt-json G [--hota] | --pan-gt-json P --truth-dir T | --davis-root V | --pvos-data V]
@@ -18,6 +19,11 @@ written as palette PNGs to O/inference/Annotations/<video>/<frame>.png (`write_v
 holds Annotations/ and ImageSets/) then scores them with evaluation.DAVISEvaluator in its semi-supervised task (davis-metrics.txt in
 O/inference), --pvos-data V (the VIPOSeg split folder) with evaluation.PVOSEvaluator (pvos-ious.txt); without either only the PNGs are
 written.
+--video-dir JPEGImages --masks-dir Annotations --dataset-name N reads a VOS data set from the folders it ships as, without a converted
+json: data.vos_records_from_dirs makes the records by the rule of N (sot_davis16*, sot_davis17*, mots_mose*, sot_ytbvos18*, pvos_viposeg*;
+--vos-meta names the folder of meta.json / obj_class.json, by default the one above --masks-dir; --reader says who decodes and counts
+the annotation PNGs) and the mapper makes the prompt masks from the PNGs' id maps (csrc/idmap_prompts.hip with --resize gpu).  Writing
+and scoring go as for the json.
 
 --png gpu has the result PNGs (the VOS id maps, the VPS panoptic maps) compressed on the device by csrc/png_deflate.hip instead of by
 Pillow on a host core: the same paths and the same pixels, mode and palette, other (larger) files; the default is host.
@@ -40,7 +46,7 @@ import sys
 import torch
 
 from .config import load_cfg
-from .data import VideoTestMapper, VOSTestMapper, is_vos_name, load_video_json, load_vos_json, video_records_from_dir
+from .data import VideoTestMapper, VOSTestMapper, is_vos_name, load_video_json, load_vos_json, video_records_from_dir, vos_records_from_dirs
 from .engine import inference_on_videos
 from .inference.results import write_vos_pngs
 from .modeling.build import build_model
@@ -54,6 +60,8 @@ def parse_args(argv=None):
     ap.add_argument("--image-root", help="the folder the file names of --json are relative to")
     ap.add_argument("--dataset-name", help="the registered name of --json's data set, e.g. ytvis_2021_val or sot_davis17_val")
     ap.add_argument("--video-dir", help="a folder whose sub-folders hold the frames of one video each")
+    ap.add_argument("--masks-dir", help="with --video-dir and --dataset-name: the folder of the videos' annotation PNGs (a VOS data set's Annotations)")
+    ap.add_argument("--vos-meta", help="with --masks-dir: the folder of meta.json / obj_class.json (default: the one above --masks-dir)")
     ap.add_argument("--output-dir", required=True)
     ap.add_argument("--resize", choices=("gpu", "host"), default="gpu")
     ap.add_argument("--decode", choices=("host", "gpu"), default="host", help="who decodes the JPEG frames: Pillow, or the HIP decoder (needs --resize gpu)")
@@ -76,13 +84,19 @@ def parse_args(argv=None):
         ap.error("give either --json (with --image-root and --dataset-name) or --video-dir")
     if from_json and not (args.image_root and args.dataset_name):
         ap.error("--json needs --image-root and --dataset-name")
+    if args.masks_dir is not None and (from_json or not args.dataset_name):
+        ap.error("--masks-dir goes with --video-dir and --dataset-name (a VOS data set in its folders), not with --json")
+    if args.vos_meta is not None and args.masks_dir is None:
+        ap.error("--vos-meta goes with --masks-dir")
     if (args.pan_gt_json is None) != (args.truth_dir is None):
         ap.error("--pan-gt-json and --truth-dir go together")
     if sum(v is not None for v in (args.gt_json, args.pan_gt_json, args.davis_root, args.pvos_data)) > 1:
         ap.error("one evaluator at a time: --gt-json, --pan-gt-json, --davis-root or --pvos-data")
     if args.hota and args.gt_json is None:
         ap.error("--hota scores against --gt-json")
-    args.vos = bool(from_json and is_vos_name(args.dataset_name))
+    if args.masks_dir is not None and not is_vos_name(args.dataset_name):
+        ap.error("--masks-dir reads a VOS data set (--dataset-name sot_*, mots_mose*, pvos_*)")
+    args.vos = bool((from_json or args.masks_dir is not None) and is_vos_name(args.dataset_name))
     if (args.davis_root or args.pvos_data) and not args.vos:
         ap.error("--davis-root and --pvos-data score a VOS data set (--dataset-name sot_*, mots_mose*, mots_burst*, pvos_*)")
     if args.vos and (args.gt_json or args.pan_gt_json):
@@ -228,7 +242,10 @@ def main(argv=None):
     ckpt = torch.load(args.weights, map_location="cpu")
     model.load_state_dict(ckpt["model"], strict=True)
     model = model.to(args.device)
-    if args.vos:
+    if args.vos and getattr(args, "masks_dir", None) is not None:
+        records = vos_records_from_dirs(args.video_dir, args.masks_dir, args.dataset_name, meta_dir=args.vos_meta, reader=args.reader,
+                                        device=args.device)
+    elif args.vos:
         records = load_vos_json(args.json, args.image_root, args.dataset_name)
     elif args.json:
         records = load_video_json(args.json, args.image_root, args.dataset_name)
