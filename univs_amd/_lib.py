@@ -1,7 +1,8 @@
 """ctypes binding of libunivs_hip.so (the C ABI declared in include/univs_hip.h, include/univs_eval_hip.h,
 include/univs_fused_hip.h, include/univs_pvos_hip.h, include/univs_semantic_hip.h, include/univs_encoder_hip.h,
 include/univs_swin_hip.h, include/univs_frames_hip.h, include/univs_prompts_hip.h, include/univs_png_hip.h,
-include/univs_hota_hip.h, include/univs_pngread_hip.h, include/univs_jpeg_hip.h, include/univs_jpegenc_hip.h and include/univs_idmap_hip.h).
+include/univs_hota_hip.h, include/univs_pngread_hip.h, include/univs_jpeg_hip.h, include/univs_jpegenc_hip.h, include/univs_idmap_hip.h
+and include/univs_seam_hip.h).
 
 The header is the one statement of the ABI: `SIGNATURES` (restype / argtypes of every `univs_*` symbol) and `CONFIG_FIELDS` (the
 members of `struct UnivsConfig`) are read from its text when this module loads -- no table is kept by hand.
@@ -132,6 +133,10 @@ with open(JPEGENC_HEADER_PATH) as _f:
 IDMAP_HEADER_PATH = os.path.join(_HERE, "..", "include", "univs_idmap_hip.h")
 with open(IDMAP_HEADER_PATH) as _f:
     IDMAP_SIGNATURES = parse_signatures(_f.read())
+# The sixteenth header (include/univs_seam_hip.h: the seams of a decoder layer, two few-rows kernels in one launch), likewise.
+SEAM_HEADER_PATH = os.path.join(_HERE, "..", "include", "univs_seam_hip.h")
+with open(SEAM_HEADER_PATH) as _f:
+    SEAM_SIGNATURES = parse_signatures(_f.read())
 
 _lib = None
 
@@ -154,7 +159,8 @@ def load():
     for name, (res, args) in (*SIGNATURES.items(), *EVAL_SIGNATURES.items(), *FUSED_SIGNATURES.items(),
                               *PVOS_SIGNATURES.items(), *SEMANTIC_SIGNATURES.items(), *ENCODER_SIGNATURES.items(), *SWIN_SIGNATURES.items(),
                               *FRAMES_SIGNATURES.items(), *PROMPTS_SIGNATURES.items(), *PNG_SIGNATURES.items(), *HOTA_SIGNATURES.items(),
-                              *PNGREAD_SIGNATURES.items(), *JPEG_SIGNATURES.items(), *JPEGENC_SIGNATURES.items(), *IDMAP_SIGNATURES.items()):
+                              *PNGREAD_SIGNATURES.items(), *JPEG_SIGNATURES.items(), *JPEGENC_SIGNATURES.items(), *IDMAP_SIGNATURES.items(),
+                              *SEAM_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing -> loud
         fn.restype = res
         fn.argtypes = args

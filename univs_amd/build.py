@@ -21,7 +21,7 @@ HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "msda_common.h"), 
            os.path.join(HERE, "..", "include", "univs_png_hip.h"), os.path.join(HERE, "..", "include", "univs_hota_hip.h"),
            os.path.join(HERE, "..", "include", "univs_pngread_hip.h"), os.path.join(HERE, "..", "include", "univs_jpeg_hip.h"),
            os.path.join(HERE, "..", "include", "univs_jpegenc_hip.h"), os.path.join(CSRC, "jpeg_huff_std.h"),
-           os.path.join(HERE, "..", "include", "univs_idmap_hip.h")]
+           os.path.join(HERE, "..", "include", "univs_idmap_hip.h"), os.path.join(HERE, "..", "include", "univs_seam_hip.h")]
 # hota_count.hip promises IEEE operations in the order written (its sums are compared bit for bit with numpy's): no contraction to fma
 SOURCE_FLAGS = {"hota_count.hip": ["-ffp-contract=off"]}
 

@@ -17,6 +17,7 @@
 #include "../../include/univs_pngread_hip.h"
 #include "../../include/univs_prompts_hip.h"
 #include "../../include/univs_pvos_hip.h"
+#include "../../include/univs_seam_hip.h"
 #include "../../include/univs_semantic_hip.h"
 #include "../../include/univs_swin_hip.h"
 #include "common.h"
@@ -988,6 +989,39 @@ int univs_idmap_prompts_u8(const uint8_t* ids, int F, int H, int W, const int32_
   if (!ids || !frame || !value || !ty || !tx || !masks || !boxes) return e.null_pointer();
   return e.covered(idmap_prompts_u8(ids, F, H, W, frame, value, N, ty, tx, Ho, Wo, masks, boxes, e.st),
                    "not covered (F H W < 2^31, N Ho Wo < 2^31)");
+}
+
+// (include/univs_seam_hip.h)
+int univs_small_seam_presplit_f32(const float* x, const void* wpa, const float* winv_a, const float* bias_a, const float* residual,
+                                  const float* ln_weight, const float* ln_bias, float ln_eps, float* t, const float* add, const void* wpb,
+                                  const float* winv_b, const float* bias_b, int n_wb, int f_off, long long M, int Ka, int Na, int Nb, int relu,
+                                  int add_features, float* y, void* stream) {
+  const Entry e("univs_small_seam_presplit_f32", stream);
+  if (M < 0 || Nb < 0 || Ka < 1 || Na < 1 || n_wb < 1 || f_off < 0 || f_off + Nb > n_wb)
+    return e.invalid("bad arguments M=%lld Ka=%d Na=%d Nb=%d n_wb=%d f_off=%d", M, Ka, Na, Nb, n_wb, f_off);
+  if (M == 0 || Nb == 0) return UNIVS_OK;
+  if (!x || !wpa || !winv_a || !residual || !ln_weight || !t || !wpb || !winv_b || !y) return e.null_pointer();
+  return e.covered(small_seam_f32(x, wpa, winv_a, bias_a, residual, ln_weight, ln_bias, ln_eps, t, add, wpb, winv_b, bias_b, n_wb, f_off, y, M,
+                                  Ka, Na, Nb, relu, add_features, e.st),
+                   "M=%lld Ka=%d Na=%d Nb=%d not covered (Ka == Na == 256, Nb %% 256 == 0, f_off %% 4 == 0, add_features %% 32 == 0, "
+                   "M <= 1 048 560, 16-byte aligned pointers)", M, Ka, Na, Nb);
+}
+
+int univs_small_mlp_seam_presplit_f32(const float* x, const float* pre_residual, const float* pre_ln_weight, const float* pre_ln_bias,
+                                      float pre_ln_eps, float* x_out, const float* side_add, const void* side_wp, const float* side_winv,
+                                      const float* side_bias, int side_n_w, int side_f_off, float* side_y, int stages,
+                                      const void* const* wp, const float* const* winv, const float* const* bias, const int* relu,
+                                      const float* in_ln_weight, const float* in_ln_bias, float in_ln_eps, float* x_normed, long long M,
+                                      int out_T, float* y, void* stream) {
+  const Entry e("univs_small_mlp_seam_presplit_f32", stream);
+  if (M < 0 || stages < 1 || stages > 3 || out_T < 0 || (side_wp && (side_n_w < 1 || side_f_off < 0 || side_f_off + 256 > side_n_w)))
+    return e.invalid("bad arguments M=%lld stages=%d out_T=%d side_n_w=%d side_f_off=%d", M, stages, out_T, side_n_w, side_f_off);
+  if (M == 0) return UNIVS_OK;
+  if (!x || !y || !wp || !winv || !bias || !relu) return e.invalid("NULL pointer");
+  return e.covered(small_chain_seam_f32(x, pre_residual, pre_ln_weight, pre_ln_bias, pre_ln_eps, x_out, side_add, side_wp, side_winv, side_bias,
+                                        side_n_w, side_f_off, side_y, stages, wp, winv, bias, relu, in_ln_weight, in_ln_bias, in_ln_eps, x_normed, y, M, out_T, e.st),
+                   "M=%lld not covered (M <= 1 048 560, out_T | M, 16-byte aligned pointers, x_normed / bias only with a LayerNorm, the "
+                   "pre-LayerNorm with weight, bias and x_out, the side stage with its weights and side_y)", M);
 }
 
 // (include/univs_png_hip.h)

@@ -95,6 +95,14 @@ int small_linear_f32(const float* x, const float* xadd, const void* wp, const fl
 int small_linear_merged_f32(const float* ws, int plan, int L, int Nb, int Hh, const void* wp, const float* winv, const float* bias, int n_w,
                             int f_off, const float* residual, const float* ln_g, const float* ln_b, float ln_eps, float* y, int N,
                             hipStream_t st);
+int small_seam_f32(const float* x, const void* wpa, const float* winv_a, const float* bias_a, const float* residual, const float* ln_g,
+                   const float* ln_b, float ln_eps, float* t, const float* add, const void* wpb, const float* winv_b, const float* bias_b,
+                   int n_wb, int f_off, float* y, long long M, int Ka, int Na, int Nb, int relu, int add_features, hipStream_t st);
+int small_chain_seam_f32(const float* x, const float* pre_res, const float* pre_g, const float* pre_b, float pre_eps, float* xr,
+                         const float* side_add, const void* side_wp, const float* side_winv, const float* side_bias, int side_nw,
+                         int side_f_off, float* side_y, int stages, const void* const* wp, const float* const* winv,
+                         const float* const* bias, const int* relu, const float* in_g, const float* in_b, float in_eps, float* xn, float* y,
+                         long long M, int out_T, hipStream_t st);
 
 // ---- cross_attn.hip: returns UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the shape or alignment is not covered, or the launch's error; cross_attention_workspace_floats: a count
 int cross_attention_f32(const float* q, const float* k, const float* v, const unsigned char* mask, const unsigned* row_flags,

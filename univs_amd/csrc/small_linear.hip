@@ -315,19 +315,56 @@ struct SlChainArgs {
   float* Xn;            // [M, 256] or null: the normalised input rows (for the callers that need `decoder_norm(x)` itself)
   float* Y;             // [M, 256] (out_T > 0: row (q, t) stored at (t, q))
   int M, out_T;
+  // the end of a decoder layer in front of the chain (both optional):
+  // PRE: the rows are x = LayerNorm(X + pre_res) -- the FFN's `norm(tgt + linear2(.))` on the library GEMM's output X --, stored to Xr (the
+  // layer's output); statistics and expressions of layer_norm_f32_kernel<64, 1, true, false> (layer_norm.hip), in its summation order
+  const float* pre_res; // [M, 256] or null
+  const float* pre_g;   // [256]
+  const float* pre_b;   // [256]
+  float pre_eps;
+  float* Xr;            // [M, 256]
+  // SIDE: side_Y = (x + side_add) W_side^T + b_side from the rows x as loaded (after PRE, before the input LayerNorm) -- the next layer's
+  // cross-attention query projection --, a stage of its own in front of the chain: own row maxima, own operand tile
+  const float* side_add;   // [M, 256] or null
+  const u32x4* side_Wp;    // pre-split [side_Nw, 256] or null (no side stage): its features [side_f_off, side_f_off + 256)
+  const float* side_winv;  // [side_Nw]
+  const float* side_bias;  // [side_Nw] or null
+  float* side_Y;           // [M, 256]
+  int side_Nw, side_f_off;
 };
+
+// layer_norm_f32_kernel<64, 1, ...>'s row sum at this workgroup's shape: that kernel holds a row's 64 four-value chunks in the 64 lanes of
+// a wave and adds them with an xor butterfly (32, 16, ..., 1); here thread (wave ks, g_, j_) holds chunks 8 ks + 2 g_ and + 1 of row j_.
+// The chunk values go through LDS, wave w replays the butterfly for rows 2 w and 2 w + 1, and every thread reads its row's total.
+__device__ __forceinline__ float sl_ln_row_total(float c0, float c1, float (&part)[16][64], float (&total)[16], int wave, int lane, int chunk,
+                                                 int j_) {
+  part[j_][chunk] = c0;
+  part[j_][chunk + 1] = c1;
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    float v = part[2 * wave + r][lane];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if (lane == 0) total[2 * wave + r] = v;
+  }
+  __syncthreads();
+  return total[j_];
+}
 
 __global__ __launch_bounds__(64 * SL_WAVES, 3) void small_chain_kernel(const SlChainArgs a) {
   constexpr int K = 256, N = 256, KS = K >> 5;
   __shared__ __attribute__((aligned(16))) u32x4 xs[2][2 * KS * 64];      // two operand tiles (ping-pong), [part][k-step][lane]
-  __shared__ unsigned rmax[3][16];
+  __shared__ unsigned rmax[4][16];                                        // the chain's stages | the side stage
   __shared__ float rstat[2][SL_WAVES][16];
+  __shared__ float pre_part[16][64], pre_total[16];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = lane & 15, g = lane >> 4;
   const int M = a.M;
   const int row0 = blockIdx.x * 16;
   const int f0 = wave * 32;
+  const bool side = a.side_Wp != nullptr;                                 // uniform
 
   u32x4 afr[SL_AHEAD][2][2];
   auto load_a = [&](const u32x4* wl, int ks, u32x4 (&d)[2][2]) __attribute__((always_inline)) {
@@ -338,10 +375,24 @@ __global__ __launch_bounds__(64 * SL_WAVES, 3) void small_chain_kernel(const SlC
     d[1][1] = p[N + 16];
   };
   const size_t wl_off = (size_t)(g * 2) * N + f0 + j;
+  // (the side stage's features are a range of a packed image: its own strides)
+  const u32x4* wl_side = a.side_Wp + (size_t)(g * 2) * a.side_Nw + a.side_f_off + f0 + j;
+  auto load_side = [&](int ks, u32x4 (&d)[2][2]) __attribute__((always_inline)) {
+    const u32x4* p = wl_side + (size_t)ks * (8 * (size_t)a.side_Nw);
+    d[0][0] = p[0];
+    d[0][1] = p[a.side_Nw];
+    d[1][0] = p[16];
+    d[1][1] = p[a.side_Nw + 16];
+  };
+  if (side) {
 #pragma unroll
-  for (int u = 0; u < SL_AHEAD; ++u) load_a(a.Wp[0] + wl_off, u, afr[u]);
+    for (int u = 0; u < SL_AHEAD; ++u) load_side(u, afr[u]);
+  } else {
+#pragma unroll
+    for (int u = 0; u < SL_AHEAD; ++u) load_a(a.Wp[0] + wl_off, u, afr[u]);
+  }
 
-  if (tid < 48) (&rmax[0][0])[tid] = 0u;
+  if (tid < 64) (&rmax[0][0])[tid] = 0u;
   __syncthreads();
   // ---- stage-0 operand: slot s_ = tid (KS * 64 = 512 slots): row j_ = s_ & 15, columns 32 ks + 8 g_
   {
@@ -350,6 +401,44 @@ __global__ __launch_bounds__(64 * SL_WAVES, 3) void small_chain_kernel(const SlC
     const int mrow = min(row0 + j_, M - 1);
     const long long off = (long long)mrow * K + 32 * ks + 8 * g_;
     f32x4 x0 = *reinterpret_cast<const f32x4*>(a.X + off), x1 = *reinterpret_cast<const f32x4*>(a.X + off + 4);
+    f32x4 w0, w1;
+    if (side && a.side_add) {                                     // (requested ahead of PRE's exchanges)
+      w0 = *reinterpret_cast<const f32x4*>(a.side_add + off);
+      w1 = *reinterpret_cast<const f32x4*>(a.side_add + off + 4);
+    } else {
+      w0 = w1 = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    if (a.pre_res) {
+#pragma clang fp contract(off)                                    // layer_norm_f32_kernel's operations as hipcc compiled them, spelled out
+      const int c = 32 * ks + 8 * g_;
+      const f32x4 pg0 = *reinterpret_cast<const f32x4*>(a.pre_g + c), pg1 = *reinterpret_cast<const f32x4*>(a.pre_g + c + 4);
+      const f32x4 pb0 = *reinterpret_cast<const f32x4*>(a.pre_b + c), pb1 = *reinterpret_cast<const f32x4*>(a.pre_b + c + 4);
+      x0 += *reinterpret_cast<const f32x4*>(a.pre_res + off);
+      x1 += *reinterpret_cast<const f32x4*>(a.pre_res + off + 4);
+      const float tot = sl_ln_row_total(0.f + ((x0[0] + x0[1]) + (x0[2] + x0[3])), 0.f + ((x1[0] + x1[1]) + (x1[2] + x1[3])), pre_part,
+                                        pre_total, wave, lane, 8 * ks + 2 * g_, j_);
+      const float mean = tot / (float)K;
+      x0 -= mean;
+      x1 -= mean;
+      const float tq = sl_ln_row_total(fmaf(x0[0], x0[0], x0[1] * x0[1]) + fmaf(x0[2], x0[2], x0[3] * x0[3]),
+                                       fmaf(x1[0], x1[0], x1[1] * x1[1]) + fmaf(x1[2], x1[2], x1[3] * x1[3]), pre_part, pre_total, wave, lane,
+                                       8 * ks + 2 * g_, j_);
+      const float rstd = 1.f / sqrtf(fmaf(1.f / (float)K, tq, a.pre_eps));
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        x0[e] = fmaf(x0[e] * rstd, pg0[e], pb0[e]);
+        x1[e] = fmaf(x1[e] * rstd, pg1[e], pb1[e]);
+      }
+      if (row0 + j_ < M) {
+        *reinterpret_cast<f32x4*>(a.Xr + off) = x0;
+        *reinterpret_cast<f32x4*>(a.Xr + off + 4) = x1;
+      }
+    }
+    if (side) {
+      w0 += x0;
+      w1 += x1;
+      atomicMax(&rmax[3][j_], l3_absmax8(w0, w1));
+    }
     if (a.in_g) {
       // nn.LayerNorm over the row: mean, then the centred second moment (two passes).  A row's 32 slots sit in the four lanes j_ + 16 g_
       // of each of the 8 waves: lane sums by permlane swaps, wave sums through LDS, added in a fixed order (deterministic)
@@ -392,12 +481,52 @@ __global__ __launch_bounds__(64 * SL_WAVES, 3) void small_chain_kernel(const SlC
     l3_split8(x0, x1, sc, h8, m8);
     xs[0][s_] = __builtin_bit_cast(u32x4, h8);
     xs[0][KS * 64 + s_] = __builtin_bit_cast(u32x4, m8);
+    if (side) {
+      l3_scale(rmax[3][j_], 14, sc, inv);
+      l3_split8(w0, w1, sc, h8, m8);
+      xs[1][s_] = __builtin_bit_cast(u32x4, h8);
+      xs[1][KS * 64 + s_] = __builtin_bit_cast(u32x4, m8);
+    }
   }
   __syncthreads();
 
   const int row = row0 + j;
   const bool row_ok = row < M;
   f32x4 v[2];
+  if (side) {
+    // the side stage: a small_linear_kernel product on its tile (xs[1]: the chain's first hand-over writes there behind a barrier)
+    float sc_, sx_inv;
+    l3_scale(rmax[3][j], 14, sc_, sx_inv);
+    const u32x4* xt = xs[1] + lane;
+    f32x4 e_wi[2], e_bi[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int f = a.side_f_off + f0 + 16 * q + 4 * g;
+      e_wi[q] = *reinterpret_cast<const f32x4*>(a.side_winv + f);
+      e_bi[q] = a.side_bias ? *reinterpret_cast<const f32x4*>(a.side_bias + f) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    f32x4 acc[2][1];
+    acc[0][0] = acc[1][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kb = 0; kb < KS; kb += SL_AHEAD) {
+#pragma unroll
+      for (int u = 0; u < SL_AHEAD; ++u) {
+        const int ks = kb + u;
+        const f16x8 bh[1] = {__builtin_bit_cast(f16x8, xt[ks * 64])}, bm[1] = {__builtin_bit_cast(f16x8, xt[KS * 64 + ks * 64])};
+        l3_mfma3_pair<1>(afr[u], bh, bm, acc[0], acc[1]);
+        __builtin_amdgcn_sched_barrier(0);
+        if (ks + SL_AHEAD < KS) load_side(ks + SL_AHEAD, afr[u]);
+        else load_a(a.Wp[0] + wl_off, ks + SL_AHEAD - KS, afr[u]);              // the chain's first fragments
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      f32x4 t = (acc[q][0] * sx_inv) * e_wi[q] + e_bi[q];
+      t += (f32x4){0.f, 0.f, 0.f, 0.f};                          // (small_linear_kernel's `+ residual` without one: -0 -> +0)
+      if (row_ok) *reinterpret_cast<f32x4*>(a.side_Y + (long long)row * N + f0 + 16 * q + 4 * g) = t;
+    }
+  }
 #pragma unroll 1
   for (int st = 0; st < a.stages; ++st) {
     float sc_, sx_inv;
@@ -464,21 +593,278 @@ __global__ __launch_bounds__(64 * SL_WAVES, 3) void small_chain_kernel(const SlC
   }
 }
 
-int small_chain_f32(const float* x, int stages, const void* const* wp, const float* const* winv, const float* const* bias, const int* relu,
-                    const float* in_g, const float* in_b, float in_eps, float* xn, float* y, long long M, int out_T, hipStream_t st) {
+// `pre_*` / `xr` and `side_*`: the two optional stages in front of the chain (SlChainArgs); all NULL: the plain chain
+int small_chain_seam_f32(const float* x, const float* pre_res, const float* pre_g, const float* pre_b, float pre_eps, float* xr,
+                         const float* side_add, const void* side_wp, const float* side_winv, const float* side_bias, int side_nw,
+                         int side_f_off, float* side_y, int stages, const void* const* wp, const float* const* winv,
+                         const float* const* bias, const int* relu, const float* in_g, const float* in_b, float in_eps, float* xn, float* y,
+                         long long M, int out_T, hipStream_t st) {
   if (M <= 0) return UNIVS_OK;
   auto mis = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
   if (stages < 1 || stages > 3 || M > 16LL * 65535 || out_T < 0 || (out_T > 0 && M % out_T != 0) || mis(x) || mis(y) || mis(xn) || mis(in_g) ||
       mis(in_b) || (in_b && !in_g) || (xn && !in_g) || M * 256LL * 4 >= 0x7FFFFFFFLL)
     return UNIVS_ERR_NOT_IMPLEMENTED;
+  if ((pre_res && (!pre_g || !pre_b || !xr)) || (!pre_res && (pre_g || pre_b || xr)) || mis(pre_res) || mis(pre_g) || mis(pre_b) || mis(xr) ||
+      (side_wp && (!side_winv || !side_y || side_nw % 4 != 0 || side_f_off % 4 != 0 || side_f_off < 0 || side_f_off + 256 > side_nw)) ||
+      (!side_wp && (side_add || side_winv || side_bias || side_y)) || mis(side_add) || mis(side_wp) ||
+      mis(side_winv) || mis(side_bias) || mis(side_y))
+    return UNIVS_ERR_NOT_IMPLEMENTED;
   SlChainArgs a{};
   a.X = x; a.stages = stages; a.in_g = in_g; a.in_b = in_b; a.in_eps = in_eps; a.Xn = xn; a.Y = y; a.M = (int)M; a.out_T = out_T;
+  a.pre_res = pre_res; a.pre_g = pre_g; a.pre_b = pre_b; a.pre_eps = pre_eps; a.Xr = xr;
+  a.side_add = side_add; a.side_Wp = reinterpret_cast<const u32x4*>(side_wp); a.side_winv = side_winv; a.side_bias = side_bias; a.side_Y = side_y;
+  a.side_Nw = side_nw; a.side_f_off = side_f_off;
   for (int s_ = 0; s_ < stages; ++s_) {
     if (!wp[s_] || !winv[s_] || mis(wp[s_]) || mis(winv[s_]) || mis(bias[s_])) return UNIVS_ERR_NOT_IMPLEMENTED;
     a.Wp[s_] = reinterpret_cast<const u32x4*>(wp[s_]); a.winv[s_] = winv[s_]; a.bias[s_] = bias[s_]; a.relu[s_] = relu[s_] ? 1 : 0;
   }
   hipLaunchKernelGGL(small_chain_kernel, dim3((unsigned)((M + 15) / 16)), dim3(64 * SL_WAVES), 0, st, a);
   return check_launch("small_chain_f32");
+}
+
+int small_chain_f32(const float* x, int stages, const void* const* wp, const float* const* winv, const float* const* bias, const int* relu,
+                    const float* in_g, const float* in_b, float in_eps, float* xn, float* y, long long M, int out_T, hipStream_t st) {
+  return small_chain_seam_f32(x, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, stages, wp, winv,
+                              bias, relu, in_g, in_b, in_eps, xn, y, M, out_T, st);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// A SEAM between two sub-layers of a post-norm decoder layer in ONE launch: t = LayerNorm(residual + x W_a^T + b_a) -- the tail of an
+// attention sub-layer, exactly small_linear_kernel<false> with its residual + LayerNorm epilogue (K = N = 256) -- and
+// y = act((t [+ add]) W_b^T + b_b), the first Linear of the NEXT sub-layer (the packed self-attention in-projection behind the
+// cross-attention, the FFN's linear1 + ReLU behind the self-attention), which reads nothing but t.  t is stored (the next residual
+// needs it) and handed over as small_chain_kernel hands a stage's rows over: the 16 x 256 rows of t [+ add, summed in fp32 registers]
+// meet their row maxima in LDS, are scaled, split and written as stage B's operand tile(s) -- the values, maxima, scales and parts a
+// separate launch would have loaded and computed, so both outputs have the bits of the two launches.  `add_features` as in SlArgs:
+// two tiles (t + add for the output features below it, t for the rest), a workgroup builds only what its features read.
+// Grid (row tiles, N_b / 256): every workgroup of a row tile recomputes stage A for its 16 rows (deterministic: the same bits in each),
+// blockIdx.y == 0 stores t -- the column groups run side by side, not behind each other in one workgroup (all of this is latency).
+struct SlSeamArgs {
+  const float* X;       // [M, 256]: stage A's operand
+  const u32x4* Wa;      // pre-split W_a [256, 256]
+  const float* winv_a;  // [256]
+  const float* bias_a;  // [256] or null
+  const float* Res;     // [M, 256]
+  const float* ln_g;    // [256]
+  const float* ln_b;    // [256] or null
+  float ln_eps;
+  float* T;             // [M, 256]
+  const float* Add;     // [M, 256] or null: stage B's operand is t + Add (`with_pos_embed`)
+  const u32x4* Wb;      // pre-split W_b [Nwb, 256]
+  const float* winv_b;  // [Nwb]
+  const float* bias_b;  // [Nwb] or null
+  float* Y;             // [M, Nb]
+  int M, Nb, Nwb, f_off, relu, add_features;   // stage B: features [f_off, f_off + Nb) of W_b, Nb % 256 == 0
+};
+
+__global__ __launch_bounds__(64 * SL_WAVES, 3) void small_seam_kernel(const SlSeamArgs a) {
+  constexpr int K = 256, N = 256, KS = K >> 5;
+  __shared__ __attribute__((aligned(16))) u32x4 xs[2][2 * KS * 64];      // [0]: stage A's operand, then the plain t tile; [1]: the t + add tile
+  __shared__ float red[2][SL_WAVES][16];
+  __shared__ unsigned rmax[3][16];                                        // stage A's operand | t + add | t
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int j = lane & 15, g = lane >> 4;
+  const int M = a.M;
+  const int row0 = blockIdx.x * 16;
+  const int f0 = wave * 32;                                     // this wave's features of stage A = its k-step of stage B's operand
+  const int fbase = blockIdx.y * N, fb0 = fbase + f0;           // its features of stage B (within [0, Nb))
+  // which operand tiles this workgroup's waves read in stage B (uniform), as small_linear_kernel: tile 1 = t + add, tile 0 = t
+  const bool need_add = a.Add != nullptr && (a.add_features == 0 || fbase < a.add_features);
+  const bool need_plain = a.Add == nullptr || (a.add_features != 0 && fbase + N > a.add_features);
+  const bool my_add = a.Add != nullptr && (a.add_features == 0 || fb0 < a.add_features);                 // wave-uniform
+
+  u32x4 afr[SL_AHEAD][2][2];
+  auto load_a = [&](const u32x4* wl, int nw, int ks, u32x4 (&d)[2][2]) __attribute__((always_inline)) {
+    const u32x4* p = wl + (size_t)ks * (8 * (size_t)nw);
+    d[0][0] = p[0];
+    d[0][1] = p[nw];
+    d[1][0] = p[16];
+    d[1][1] = p[nw + 16];
+  };
+  const u32x4* wla = a.Wa + (size_t)(g * 2) * N + f0 + j;
+  const u32x4* wlb = a.Wb + (size_t)(g * 2) * a.Nwb + a.f_off + fb0 + j;
+#pragma unroll
+  for (int u = 0; u < SL_AHEAD; ++u) load_a(wla, N, u, afr[u]);
+
+  if (tid < 48) (&rmax[0][0])[tid] = 0u;
+  __syncthreads();
+  // ---- stage A's operand: slot s_ = tid: row j_ = s_ & 15, columns 32 ks + 8 g_ (small_linear_kernel's staging, one plain tile)
+  {
+    const int s_ = tid;
+    const int ks = s_ >> 6, l_ = s_ & 63, j_ = l_ & 15, g_ = l_ >> 4;
+    const long long off = (long long)min(row0 + j_, M - 1) * K + 32 * ks + 8 * g_;
+    const f32x4 x0 = *reinterpret_cast<const f32x4*>(a.X + off), x1 = *reinterpret_cast<const f32x4*>(a.X + off + 4);
+    atomicMax(&rmax[0][j_], l3_absmax8(x0, x1));
+    __syncthreads();
+    float sc, inv;
+    l3_scale(rmax[0][j_], 14, sc, inv);
+    f16x8 h8, m8;
+    l3_split8(x0, x1, sc, h8, m8);
+    xs[0][s_] = __builtin_bit_cast(u32x4, h8);
+    xs[0][KS * 64 + s_] = __builtin_bit_cast(u32x4, m8);
+  }
+  __syncthreads();
+
+  const int m = min(row0 + j, M - 1);
+  const int row = row0 + j;
+  const bool row_ok = row < M;
+  f32x4 v[2], w[2], eb_wi[2], eb_bi[2];                          // t, t + add, stage B's epilogue operands
+  {
+    float sc_, sx_inv;
+    l3_scale(rmax[0][j], 14, sc_, sx_inv);
+    f32x4 e_wi[2], e_bi[2], e_res[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int f = f0 + 16 * q + 4 * g;
+      e_wi[q] = *reinterpret_cast<const f32x4*>(a.winv_a + f);
+      e_bi[q] = a.bias_a ? *reinterpret_cast<const f32x4*>(a.bias_a + f) : (f32x4){0.f, 0.f, 0.f, 0.f};
+      e_res[q] = *reinterpret_cast<const f32x4*>(a.Res + (long long)m * N + f);
+    }
+    const u32x4* xt = xs[0] + lane;
+    f32x4 acc[2][1];
+    acc[0][0] = acc[1][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kb = 0; kb < KS; kb += SL_AHEAD) {
+#pragma unroll
+      for (int u = 0; u < SL_AHEAD; ++u) {
+        const int ks = kb + u;
+        const f16x8 bh[1] = {__builtin_bit_cast(f16x8, xt[ks * 64])}, bm[1] = {__builtin_bit_cast(f16x8, xt[KS * 64 + ks * 64])};
+        l3_mfma3_pair<1>(afr[u], bh, bm, acc[0], acc[1]);
+        __builtin_amdgcn_sched_barrier(0);
+        if (ks + SL_AHEAD < KS) load_a(wla, N, ks + SL_AHEAD, afr[u]);
+        else load_a(wlb, a.Nwb, ks + SL_AHEAD - KS, afr[u]);     // stage B's first fragments, ahead of the hand-over's barriers
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    // what the hand-over and stage B's epilogue read, requested ahead of the LayerNorm's two exchanges
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int f = a.f_off + fb0 + 16 * q + 4 * g;
+      eb_wi[q] = *reinterpret_cast<const f32x4*>(a.winv_b + f);
+      eb_bi[q] = a.bias_b ? *reinterpret_cast<const f32x4*>(a.bias_b + f) : (f32x4){0.f, 0.f, 0.f, 0.f};
+      w[q] = need_add ? *reinterpret_cast<const f32x4*>(a.Add + (long long)m * N + f0 + 16 * q + 4 * g) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    // the epilogue of small_linear_kernel with a residual and a LayerNorm, expression by expression
+    float sm = 0.f;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      f32x4 t = (acc[q][0] * sx_inv) * e_wi[q] + e_bi[q];
+      t += e_res[q];
+      v[q] = t;
+      sm += (v[q][0] + v[q][1]) + (v[q][2] + v[q][3]);
+    }
+    const float inv_n = 1.0f / (float)N;
+    const float ws = sl_row_sum(sm);
+    if (g == 0) red[0][wave][j] = ws;
+    __syncthreads();                                              // (every wave is done with stage A's tile here)
+    float tot = 0.f;
+#pragma unroll
+    for (int w = 0; w < SL_WAVES; ++w) tot += red[0][w][j];
+    const float mean = tot * inv_n;
+    float sq = 0.f;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      v[q] -= mean;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) sq = fmaf(v[q][e], v[q][e], sq);
+    }
+    const float wq = sl_row_sum(sq);
+    if (g == 0) red[1][wave][j] = wq;
+    __syncthreads();
+    float tq = 0.f;
+#pragma unroll
+    for (int w = 0; w < SL_WAVES; ++w) tq += red[1][w][j];
+    const float rstd = 1.0f / sqrtf(tq * inv_n + a.ln_eps);
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int f = f0 + 16 * q + 4 * g;
+      const f32x4 gm = *reinterpret_cast<const f32x4*>(a.ln_g + f);
+      f32x4 y = (v[q] * rstd) * gm;
+      if (a.ln_b) y += *reinterpret_cast<const f32x4*>(a.ln_b + f);
+      v[q] = y;
+    }
+  }
+  if (blockIdx.y == 0 && row_ok) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) *reinterpret_cast<f32x4*>(a.T + (long long)row * N + f0 + 16 * q + 4 * g) = v[q];
+  }
+
+  // ---- hand-over: the rows of t (+ add) become stage B's operand tile(s): small_chain_kernel's, once per tile
+  if (need_add) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) w[q] = v[q] + w[q];
+    atomicMax(&rmax[1][j], l3_absmax8(w[0], w[1]));
+  }
+  if (need_plain) atomicMax(&rmax[2][j], l3_absmax8(v[0], v[1]));
+  __syncthreads();
+  auto hand_over = [&](const f32x4 (&r)[2], unsigned maxbits, u32x4* tile) __attribute__((always_inline)) {
+    float sc, inv;
+    l3_scale(maxbits, 14, sc, inv);
+    _Float16* dst = reinterpret_cast<_Float16*>(tile);
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+      h4 hh, mm;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float xsv = r[q][e] * sc;
+        hh[e] = (_Float16)xsv;
+        mm[e] = (_Float16)(xsv - (float)hh[e]);
+      }
+      const int unit = wave * 64 + (2 * q + (g >> 1)) * 16 + j;             // k-step = this wave's 32 features
+      *reinterpret_cast<h4*>(dst + (size_t)unit * 8 + 4 * (g & 1)) = hh;
+      *reinterpret_cast<h4*>(dst + (size_t)(KS * 64 + unit) * 8 + 4 * (g & 1)) = mm;
+    }
+  };
+  if (need_add) hand_over(w, rmax[1][j], xs[1]);
+  if (need_plain) hand_over(v, rmax[2][j], xs[0]);
+  __syncthreads();
+
+  // ---- stage B
+  float sc_, sx_inv;
+  l3_scale(rmax[my_add ? 1 : 2][j], 14, sc_, sx_inv);
+  const u32x4* xt = xs[my_add ? 1 : 0] + lane;
+  f32x4 acc[2][1];
+  acc[0][0] = acc[1][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int kb = 0; kb < KS; kb += SL_AHEAD) {
+#pragma unroll
+    for (int u = 0; u < SL_AHEAD; ++u) {
+      const int ks = kb + u;
+      const f16x8 bh[1] = {__builtin_bit_cast(f16x8, xt[ks * 64])}, bm[1] = {__builtin_bit_cast(f16x8, xt[KS * 64 + ks * 64])};
+      l3_mfma3_pair<1>(afr[u], bh, bm, acc[0], acc[1]);
+      __builtin_amdgcn_sched_barrier(0);
+      if (ks + SL_AHEAD < KS) load_a(wlb, a.Nwb, ks + SL_AHEAD, afr[u]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    f32x4 t = (acc[q][0] * sx_inv) * eb_wi[q] + eb_bi[q];
+    if (a.relu) t = __builtin_elementwise_maximum(t, (f32x4){0.f, 0.f, 0.f, 0.f});   // NaN-propagating, as torch.relu
+    t += (f32x4){0.f, 0.f, 0.f, 0.f};                            // (small_linear_kernel's `+ residual` without one: -0 -> +0)
+    if (row_ok) *reinterpret_cast<f32x4*>(a.Y + (long long)row * a.Nb + fb0 + 16 * q + 4 * g) = t;
+  }
+}
+
+// returns UNIVS_OK, or UNIVS_ERR_NOT_IMPLEMENTED when the shape is not covered
+int small_seam_f32(const float* x, const void* wpa, const float* winv_a, const float* bias_a, const float* residual, const float* ln_g,
+                   const float* ln_b, float ln_eps, float* t, const float* add, const void* wpb, const float* winv_b, const float* bias_b,
+                   int n_wb, int f_off, float* y, long long M, int Ka, int Na, int Nb, int relu, int add_features, hipStream_t st) {
+  if (M <= 0 || Nb <= 0) return UNIVS_OK;
+  auto mis = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+  if (Ka != SL_KMAX || Na != 32 * SL_WAVES || Nb % (32 * SL_WAVES) != 0 || n_wb % 4 != 0 || f_off % 4 != 0 || f_off < 0 || f_off + Nb > n_wb ||
+      M > 16LL * 65535 || Nb / (32 * SL_WAVES) > 65535 || add_features < 0 || add_features % 32 != 0 || mis(x) || mis(wpa) || mis(winv_a) ||
+      mis(bias_a) || mis(residual) || mis(ln_g) || mis(ln_b) || mis(t) || mis(add) || mis(wpb) || mis(winv_b) || mis(bias_b) || mis(y) ||
+      M * (long long)std::max(Nb, Ka) * 4 >= 0x7FFFFFFFLL)
+    return UNIVS_ERR_NOT_IMPLEMENTED;
+  SlSeamArgs a{};
+  a.X = x; a.Wa = reinterpret_cast<const u32x4*>(wpa); a.winv_a = winv_a; a.bias_a = bias_a; a.Res = residual; a.ln_g = ln_g; a.ln_b = ln_b;
+  a.ln_eps = ln_eps; a.T = t; a.Add = add; a.Wb = reinterpret_cast<const u32x4*>(wpb); a.winv_b = winv_b; a.bias_b = bias_b; a.Y = y;
+  a.M = (int)M; a.Nb = Nb; a.Nwb = n_wb; a.f_off = f_off; a.relu = relu ? 1 : 0; a.add_features = add_features;
+  hipLaunchKernelGGL(small_seam_kernel, dim3((unsigned)((M + 15) / 16), (unsigned)(Nb / (32 * SL_WAVES))), dim3(64 * SL_WAVES), 0, st, a);
+  return check_launch("small_seam_f32");
 }
 
 }  // namespace univs

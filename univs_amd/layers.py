@@ -165,12 +165,18 @@ class MultiheadAttention(nn.Module):
         return d
 
     def forward(self, query, key, value, attn_mask: Optional[torch.Tensor] = None, need_weights=False,
-                average_attn_weights=True, kv=None, query_add=None, residual=None, norm=None):
+                average_attn_weights=True, kv=None, query_add=None, residual=None, norm=None, in_proj=None, next_linear=None):
         """`kv` = (k, v) [S, N, E]: the key / value projections when the caller already has them (the decoder computes the K and V
         of all layers that attend to one feature level with ONE Linear each; `key` / `value` are then ignored).
         `query_add`: the query (and, where `key is query`, the key) operand is `query + query_add` -- the layer's `with_pos_embed`
         inside the projection kernel; `residual` + `norm` (an nn.LayerNorm): the first result is `norm(residual + out_proj(.))` --
-        the post-norm layer's tail inside the output projection's kernel (transformer_layers.py:42-46, :106-110)."""
+        the post-norm layer's tail inside the output projection's kernel (transformer_layers.py:42-46, :106-110).
+        The seams of a decoder layer (SWITCHES.decoder_seams; seam_ops.small_seam):
+        `in_proj`: this call's in-projection as the launch in front of it already computed it -- q [L, N, E] beside `kv`, or the packed
+        q | k | v [L, N, 3 E] of a self-attention with positional queries; the caller vouches that it is this module's projection of `query`.
+        `next_linear` = (weight, bias, add, relu, add_features) (with `residual` + `norm`): the Linear that reads nothing but this call's
+        first result, computed in the output projection's launch; the call then returns (out, weights, y) with y = act((out [+ add])
+        weight^T + bias) -- or None where that launch does not cover it, and the caller runs its Linear itself."""
         L, N, E = query.shape
         S = key.shape[0] if kv is None else kv[0].shape[0]
         h, d = self.num_heads, self.head_dim
@@ -188,8 +194,10 @@ class MultiheadAttention(nn.Module):
             wr, br = self._packed_rows(r0, n)
             return linear(x if add is None else x + add, wr, br)
         if kv is not None:
-            q = lin(query, 0, E, query_add)
+            q = in_proj if in_proj is not None else lin(query, 0, E, query_add)
             k, v = kv
+        elif in_proj is not None:
+            q, k, v = in_proj.chunk(3, dim=-1)
         elif query is key and key is value and query_add is None:
             q, k, v = lin(query, 0, 3 * E).chunk(3, dim=-1)
         else:
@@ -211,11 +219,24 @@ class MultiheadAttention(nn.Module):
                     k = lin(key, E, E)
                     v = lin(value, 2 * E, E)
 
+        nxt = [None]
+
         def project(out):
             if norm is None:
                 y = linear(out, self.out_proj.weight, self.out_proj.bias)
                 return y if residual is None else residual + y
+            if next_linear is not None and out.is_cuda and _small(out, self.out_proj.weight, self.out_proj.bias):
+                from . import seam_ops
+                wn, bn, addn, relun, afn = next_linear
+                r = seam_ops.small_seam(out, self.out_proj.weight, self.out_proj.bias, residual, (norm.weight, norm.bias, norm.eps), wn, bn,
+                                        add=addn, relu=relun, add_features=afn)
+                if r is not None:
+                    nxt[0] = r[1]
+                    return r[0]
             return linear_norm(out, self.out_proj, residual, norm)
+
+        def result(out, weights):
+            return (out, weights) if next_linear is None else (out, weights, nxt[0])
         if (SWITCHES.fused_cross_attention and query.is_cuda and not need_weights and d == 32 and S >= 64 and L <= 2048
                 and (attn_mask is None or (attn_mask.dtype in (torch.bool, torch.uint8)
                                            and ((attn_mask.dim() == 3 and attn_mask.shape[0] == N) or (attn_mask.dim() == 2 and N == 1))))):
@@ -236,10 +257,10 @@ class MultiheadAttention(nn.Module):
                 tail = dict(residual=residual, ln=(norm.weight, norm.bias, norm.eps)) if norm is not None else {}
                 y = fused_ops.attention_out_proj(q, k, v, m3, h, 1.0 / math.sqrt(d), self.out_proj.weight, self.out_proj.bias, **tail)
                 if y is not None:
-                    return (y if norm is not None or residual is None else residual + y), None
+                    return result((y if norm is not None or residual is None else residual + y), None)
             out = ops.cross_attention(q, k, v, m3, h, 1.0 / math.sqrt(d))
             if out is not None:
-                return project(out), None
+                return result(project(out), None)
         if attn_mask is not None and not isinstance(attn_mask, torch.Tensor):
             attn_mask = attn_mask.materialize()                  # ops.DeferredMask: the paths below read the reference's tensor
         # [L, N, h, d] -> [N, h, L, d]
@@ -265,8 +286,8 @@ class MultiheadAttention(nn.Module):
         out = out.permute(2, 0, 1, 3).reshape(L, N, E)
         out = project(out)
         if need_weights:
-            return out, (attn.mean(dim=1) if average_attn_weights else attn)
-        return out, None
+            return result(out, (attn.mean(dim=1) if average_attn_weights else attn))
+        return result(out, None)
 
 
 class MLP(nn.Module):
@@ -278,23 +299,50 @@ class MLP(nn.Module):
         h = [hidden_dim] * (num_layers - 1)
         self.layers = nn.ModuleList(nn.Linear(n, k) for n, k in zip([input_dim] + h, h + [output_dim]))
 
-    def forward(self, x, transpose01=False, in_norm=None, want_normed=False):
+    def forward(self, x, transpose01=False, in_norm=None, want_normed=False, pre_norm=None, side=None):
         """`transpose01`: x is [A, B, C]; the result comes back as [B, A, C'] -- contiguous where the last Linear's kernel writes it that
         way (few rows on the GPU), a transposed view otherwise.  `in_norm` (an nn.LayerNorm): the MLP is applied to `in_norm(x)`; with
         `want_normed` the call returns (y, in_norm(x)).  Few rows of 256 channels on the GPU: the whole chain -- LayerNorm included -- is
-        ONE launch (ops.small_mlp)."""
+        ONE launch (ops.small_mlp).
+        The seams of a decoder layer (SWITCHES.decoder_seams): `pre_norm` = (residual, an nn.LayerNorm): the input rows are
+        x' = norm(x + residual) -- the FFN's tail on its second Linear's output --; `side` = (weight, bias, rows, add): the Linear
+        (x' [+ add]) weight[rows]^T + bias[rows] that reads the same rows (the next layer's cross-attention query projection).  With either
+        the call returns (y[, in_norm(x')], x', side_y) -- x' is x without `pre_norm`, side_y None without `side` --, from the chain's one
+        launch where ops.small_mlp covers it."""
+        seam = pre_norm is not None or side is not None
         if (SWITCHES.small_mlp_chain and x.is_cuda and self.num_layers <= 3 and x.shape[-1] == 256 and not torch.is_grad_enabled()
                 and x.numel() // 256 <= 4096 and (in_norm is None or SWITCHES.small_mlp_norm)):
             from . import ops
             chain = [(l_.weight, l_.bias, i < self.num_layers - 1) for i, l_ in enumerate(self.layers)]
-            r = ops.small_mlp(x, chain, in_ln=None if in_norm is None else (in_norm.weight, in_norm.bias, in_norm.eps),
-                              want_normed=want_normed, transpose01=transpose01)
-            if r is not None:
-                return r
+            in_ln = None if in_norm is None else (in_norm.weight, in_norm.bias, in_norm.eps)
+            if seam:
+                pre_ln = None if pre_norm is None else (pre_norm[0], pre_norm[1].weight, pre_norm[1].bias, pre_norm[1].eps)
+                r = ops.small_mlp(x, chain, in_ln=in_ln, want_normed=want_normed, transpose01=transpose01, pre_ln=pre_ln, side=side)
+                if r is not None:
+                    r = list(r)
+                    head = [r.pop(0)] + ([r.pop(0)] if want_normed else [])
+                    return (*head, r.pop(0) if pre_norm is not None else x, r.pop(0) if side is not None else None)
+            else:
+                r = ops.small_mlp(x, chain, in_ln=in_ln, want_normed=want_normed, transpose01=transpose01)
+                if r is not None:
+                    return r
+        side_y = None
+        if pre_norm is not None:
+            x = layer_norm(pre_norm[1], x, residual=pre_norm[0])
+        if side is not None:
+            from . import ops
+            sw, sb, srows, sadd = side
+            side_y = ops.small_linear(x, sw, sb, rows=srows, x_add=sadd) if x.is_cuda and _small(x, sw, sb) else None
+            if side_y is None:
+                r0, n = (0, sw.shape[0]) if srows is None else srows
+                side_y = linear(x if sadd is None else x + sadd, sw[r0:r0 + n], None if sb is None else sb[r0:r0 + n])
+        x_in = x
         xn = None
         if in_norm is not None:
             x = xn = in_norm(x)
         y = self._forward_layers(x, transpose01)
+        if seam:
+            return (y, xn, x_in, side_y) if want_normed else (y, x_in, side_y)
         return (y, xn) if want_normed else y
 
     def _forward_layers(self, x, transpose01):

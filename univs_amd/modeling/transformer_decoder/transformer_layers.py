@@ -21,11 +21,21 @@ class SelfAttentionLayer(nn.Module):
         self.normalize_before = normalize_before
 
     def forward(self, tgt, tgt_mask: Optional[Tensor] = None, tgt_key_padding_mask: Optional[Tensor] = None,
-                query_pos: Optional[Tensor] = None, kv: Optional[Tensor] = None, kv_pos: Optional[Tensor] = None):
+                query_pos: Optional[Tensor] = None, kv: Optional[Tensor] = None, kv_pos: Optional[Tensor] = None,
+                in_proj: Optional[Tensor] = None, next_linear=None):
         """`kv` / `kv_pos` (frame-sharded decoding, univs_amd/distributed.py): `tgt` then holds only SOME of the tokens -- this
         rank's query rows -- and attends to the keys / values of ALL tokens in `kv`; `tgt_mask` is [rows, all].  Row r of the
-        result equals row r of the full self-attention (…decoder_univs.py:408-414): softmax rows are independent."""
+        result equals row r of the full self-attention (…decoder_univs.py:408-414): softmax rows are independent.
+        The seams of the decoder layer (post-norm, all tokens, positional queries; layers.MultiheadAttention.forward): `in_proj` is the
+        packed q | k | v projection of `tgt` (+ `query_pos` for q and k) where the launch in front already computed it; with
+        `next_linear` = (weight, bias, add, relu, add_features) the call returns (tgt, y): y is that Linear of the new `tgt`, or None
+        where the output projection's launch did not take it along."""
         assert tgt_key_padding_mask is None
+        if next_linear is not None or in_proj is not None:
+            assert kv is None and not self.normalize_before and query_pos is not None
+            r = self.self_attn(tgt, tgt, tgt, attn_mask=tgt_mask, query_add=query_pos, residual=tgt, norm=self.norm, in_proj=in_proj,
+                               next_linear=next_linear)
+            return r[0] if next_linear is None else (r[0], r[2])
         if kv is None:
             kv, kv_pos = tgt, query_pos
             full = True
@@ -59,11 +69,20 @@ class CrossAttentionLayer(nn.Module):
 
     def forward(self, tgt, memory, memory_mask: Optional[Tensor] = None,
                 memory_key_padding_mask: Optional[Tensor] = None, pos: Optional[Tensor] = None,
-                query_pos: Optional[Tensor] = None, key: Optional[Tensor] = None, kv=None):
+                query_pos: Optional[Tensor] = None, key: Optional[Tensor] = None, kv=None, in_proj: Optional[Tensor] = None,
+                next_linear=None):
         """`key`: optional precomputed `memory + pos` (it does not change across the decoder layers that
         attend to the same feature level, so the caller builds it once per level); `kv`: optional precomputed key / value
-        PROJECTIONS of this layer (layers.MultiheadAttention.forward)."""
+        PROJECTIONS of this layer (layers.MultiheadAttention.forward).
+        The seams of the decoder layer (post-norm, with `kv`, without attention weights): `in_proj` is the query projection of
+        `tgt + query_pos` where the launch in front already computed it; with `next_linear` = (weight, bias, add, relu, add_features)
+        the call returns (tgt, y): y is that Linear of the new `tgt`, or None where the output projection's launch did not take it along."""
         assert memory_key_padding_mask is None
+        if next_linear is not None or in_proj is not None:
+            assert kv is not None and not self.normalize_before and not self.need_weights
+            r = self.multihead_attn(tgt, key, memory, attn_mask=memory_mask, kv=kv, query_add=query_pos, residual=tgt, norm=self.norm,
+                                    in_proj=in_proj, next_linear=next_linear)
+            return r[0] if next_linear is None else (r[0], r[2])
         src = layer_norm(self.norm, tgt) if self.normalize_before else tgt
         # nn.MultiheadAttention's default averages the returned weights over heads; the reference
         # never passes `average_attn_weights` through, so neither do we (transformer_layers.py:101-105)
@@ -87,7 +106,14 @@ class FFNLayer(nn.Module):
         self.activation = get_activation_fn(activation)
         self.normalize_before = normalize_before
 
-    def forward(self, tgt):
+    def forward(self, tgt, hidden: Optional[Tensor] = None, defer_norm=False):
+        """The seams of the decoder layer (post-norm): `hidden` is `activation(linear1(tgt))` where the launch in front already computed
+        it; `defer_norm`: the call returns `linear2(.)` alone and the caller's next launch applies `norm(tgt + .)` (layers.MLP.forward:
+        `pre_norm`)."""
         if self.normalize_before:
+            assert hidden is None and not defer_norm
             return tgt + self.linear2(linear_act(layer_norm(self.norm, tgt), self.linear1, self.activation))
-        return linear_norm(linear_act(tgt, self.linear1, self.activation), self.linear2, tgt, self.norm)
+        h = hidden if hidden is not None else linear_act(tgt, self.linear1, self.activation)
+        if defer_norm:
+            return linear(h, self.linear2.weight, self.linear2.bias)
+        return linear_norm(h, self.linear2, tgt, self.norm)

@@ -311,17 +311,54 @@ class VideoMultiScaleMaskedTransformerDecoderUniVS(nn.Module):
         predictions_class, predictions_mask, predictions_embds, predictions_reid = [], [], [], []
         want_full = self.return_aux_outputs
 
-        def heads(out_tokens, target_size, last):
-            cls_, msk_, attn_, reid_ = self.forward_prediction_heads(
+        def heads(out_tokens, target_size, last, pre_norm=None, side=None):
+            # `pre_norm` / `side`: the seams at the end of a decoder layer (forward_prediction_heads); the head's input and the side
+            # Linear's output then come back beside the attention mask
+            r = self.forward_prediction_heads(
                 out_tokens, mf, feat_lowres[target_size], task, targets, t, need_masks=(last or want_full),
-                t_total=t_total, need_class=(last or want_full), deferred_mask=SWITCHES.fused_cross_attention and not last)
+                t_total=t_total, need_class=(last or want_full), deferred_mask=SWITCHES.fused_cross_attention and not last,
+                pre_norm=pre_norm, side=side)
+            cls_, msk_, attn_, reid_ = r[:4]
+            if len(r) > 4:
+                out_tokens = r[4]
             predictions_class.append(cls_)
             predictions_mask.append(msk_)
             predictions_embds.append(out_tokens.view(out_tokens.shape[0], bs, t, -1).permute(1, 0, 2, 3))
             predictions_reid.append(reid_)
-            return attn_
+            return attn_ if len(r) == 4 else (attn_, out_tokens, r[5])
 
-        attn_mask = heads(output, size_list[0], self.num_layers == 0)
+        # SWITCHES.decoder_seams: where a few-rows kernel's output is the next few-rows kernel's only input, both run in one launch --
+        # the cross-attention's tail with the self-attention's packed in-projection, the self-attention's tail with the FFN's
+        # linear1 + ReLU, the FFN's LayerNorm with the head's chain, the next layer's cross-attention query projection beside that chain
+        # (seam_ops; bit-identical).  All tokens on this rank, post-norm layers, the K / V projections precomputed, no autograd; a
+        # projection computed ahead is handed to its consumer HERE and used only if the consumer's input is the very tensor it was made of
+        ca, sa, ffn = self.transformer_cross_attention_layers, self.transformer_self_attention_layers, self.transformer_ffn_layers
+        E_ = ca[0].multihead_attn.embed_dim if self.num_layers else 0
+        seams = (SWITCHES.decoder_seams and SWITCHES.small_linear and self.num_layers > 0 and fs is None and output.is_cuda
+                 and output.dtype == torch.float32 and not torch.is_grad_enabled() and E_ == 256 and output.shape[-1] == 256
+                 and output.shape[0] * bt <= 4096
+                 and not any(l_.normalize_before or l_.need_weights for l_ in ca)
+                 and not any(l_.normalize_before for l_ in sa)
+                 and not any(l_.normalize_before or l_.activation is not F.relu or l_.linear1.bias is None for l_ in ffn))
+
+        def q_side(i_next, tokens):
+            # the query projection of cross-attention layer `i_next` as a side Linear of the head in front of it -- unless a ProCA
+            # layer rewrites the prompt queries in between
+            if not seams or i_next >= self.num_layers:
+                return None
+            if self.prompt_as_queries and 0 < i_next < self.prompt_self_attn_layers and tokens.shape[0] != self.num_queries:
+                return None
+            m_ = ca[i_next].multihead_attn
+            return (m_.in_proj_weight, m_.in_proj_bias, (0, E_), query_embed)
+
+        side0 = q_side(0, output)
+        q_ahead = None                      # (the tensor it was made of, the projection)
+        if side0 is not None:
+            attn_mask, output_h, q0 = heads(output, size_list[0], self.num_layers == 0, side=side0)
+            if q0 is not None:
+                q_ahead = (output, q0)      # (no pre_norm: the head's input is `output` itself)
+        else:
+            attn_mask = heads(output, size_list[0], self.num_layers == 0)
         num_queries_lp = output.shape[0]
         self_attn_mask = self.generate_self_attn_mask(bs, t_total, num_queries_lp, dev, targets[0]["dataset_name"], task)
         query_embed_all = query_embed if fs is None else fs.all_gather_frames(query_embed, dim=1)
@@ -338,6 +375,15 @@ class VideoMultiScaleMaskedTransformerDecoderUniVS(nn.Module):
                 output = self.forward_transformer_prompt_self_attention_layer(
                     i, output, query_embed, prompt_feats_dense, prompt_pe_dense)
             lvl = i % self.num_feature_levels
+            if seams and kv_proj is not None:
+                output = self._layer_with_seams(i, output, query_embed, q_ahead, mem[lvl], mem_key[lvl], attn_mask, kv_proj[i],
+                                                self_attn_mask, bs, t)
+                last = i == self.num_layers - 1
+                side_i = q_side(i + 1, output[0])
+                attn_mask, out_new, q_next = heads(output[1], size_list[(i + 1) % self.num_feature_levels], last,
+                                                   pre_norm=(output[0], ffn[i].norm), side=side_i)
+                output, q_ahead = out_new, (None if q_next is None else (out_new, q_next))
+                continue
             # per-frame masked cross-attention; attn_mask [T, Q', HW_l] (rows already reset per :390)
             output = self.transformer_cross_attention_layers[i](
                 output, mem[lvl], memory_mask=attn_mask, pos=None, query_pos=query_embed, key=mem_key[lvl],
@@ -383,6 +429,26 @@ class VideoMultiScaleMaskedTransformerDecoderUniVS(nn.Module):
             out.update({"pred_embds": predictions_embds[-1][0].permute(1, 2, 0),
                         "mask_features": mask_features.view(bs, t, c_m, h_m, w_m)[0]})
         return out
+
+    def _layer_with_seams(self, i, output, query_embed, q_ahead, mem, mem_key, attn_mask, kv, self_attn_mask, bs, t):
+        """Cross-attention, self-attention and the FFN's two Linears of decoder layer i with the seams between them in one launch each
+        (SWITCHES.decoder_seams; the layer loop of `forward` states when).  Returns (tgt, y): the self-attention's output and
+        `linear2(relu(linear1(tgt)))` -- the FFN's `norm(tgt + y)` is the next prediction head's first step.  Every projection handed
+        along is used only where its consumer's launch did take it along; else the consumer computes its own."""
+        ca, sa, ffn = self.transformer_cross_attention_layers[i], self.transformer_self_attention_layers[i], self.transformer_ffn_layers[i]
+        E = ca.multihead_attn.embed_dim
+        Qn = output.shape[0]
+        q_in = q_ahead[1] if q_ahead is not None and q_ahead[0] is output else None
+        m_sa = sa.self_attn
+        output, qkv = ca(output, mem, memory_mask=attn_mask, pos=None, query_pos=query_embed, key=mem_key, kv=kv, in_proj=q_in,
+                         next_linear=(m_sa.in_proj_weight, m_sa.in_proj_bias, query_embed, False, 2 * E))
+        # spatio-temporal self-attention over Q'*T tokens: 'Q (B T) C -> (Q T) B C' (the same rows in the same order)
+        o, hid = sa(output.reshape(Qn * t, bs, -1), tgt_mask=self_attn_mask, query_pos=query_embed.reshape(Qn * t, bs, -1),
+                    in_proj=None if qkv is None else qkv.reshape(Qn * t, bs, -1),
+                    next_linear=(ffn.linear1.weight, ffn.linear1.bias, None, True, 0))
+        output = o.reshape(Qn, bs * t, -1)
+        y = ffn(output, hidden=None if hid is None else hid.reshape(Qn, bs * t, -1), defer_norm=True)
+        return output, y
 
     # ---------------------------------------------------------------------------------------------
     def forward_transformer_prompt_self_attention_layer(self, i, output, query_emb, prompt_feats_dense,
@@ -477,9 +543,12 @@ class VideoMultiScaleMaskedTransformerDecoderUniVS(nn.Module):
         return c
 
     def forward_prediction_heads(self, output, mask_features, feat_lowres, task, targets, t, need_masks,
-                                 t_total=None, need_class=True, deferred_mask=False):
+                                 t_total=None, need_class=True, deferred_mask=False, pre_norm=None, side=None):
         """:498-567.  output [Q', T, C] (batch 1); mask_features [T, C, H, W]; feat_lowres [T, C, h, w].
-        Returns (class logits [1,Q',K], mask logits [1,Q',T,H,W] or None, attn mask bool [T,Q',hw], reid)."""
+        Returns (class logits [1,Q',K], mask logits [1,Q',T,H,W] or None, attn mask bool [T,Q',hw], reid).
+        The seams of a decoder layer (layers.MLP.forward): with `pre_norm` = (residual, an nn.LayerNorm) the head's input is
+        norm(output + residual), the FFN's tail; `side` = (weight, bias, rows, add) is a Linear of that input, the next layer's
+        cross-attention query projection.  With either, two more results: the head's input and the side Linear's output (or None)."""
         bs = 1
         fs = self.frame_shard
         t_total = t if t_total is None else t_total
@@ -493,7 +562,13 @@ class VideoMultiScaleMaskedTransformerDecoderUniVS(nn.Module):
         # heads below: on the GPU norm + MLP are one launch (layers.MLP: ops.small_mlp), and the normalised rows are written out only
         # where somebody reads them
         need_normed = need_class or (self.prompt_as_queries and task == "grounding")
-        me = self.mask_embed(output, transpose01=True, in_norm=self.decoder_norm, want_normed=need_normed)
+        seam = pre_norm is not None or side is not None
+        if seam:
+            me = self.mask_embed(output, transpose01=True, in_norm=self.decoder_norm, want_normed=need_normed, pre_norm=pre_norm, side=side)
+            output, side_out = me[-2:]
+            me = me[:-2] if need_normed else me[0]
+        else:
+            me = self.mask_embed(output, transpose01=True, in_norm=self.decoder_norm, want_normed=need_normed)
         mask_embed_early, decoder_qt = me if need_normed else (me, None)
         decoder_output = decoder_qt.transpose(0, 1) if decoder_qt is not None else None   # [T, Q', C] (a view)
         # class logits of the intermediate layers are only ever returned as aux outputs (the attention mask of the next
@@ -531,6 +606,8 @@ class VideoMultiScaleMaskedTransformerDecoderUniVS(nn.Module):
         # [T, Q', hw] bool; `deferred_mask` (the layer loop): an ops.DeferredMask -- the fully-masked-row rule is applied by the
         # cross-attention kernel that reads the mask, not by a pass of its own
         attn_mask = ops.mask_decode_attn(mask_embed, feat_lowres, deferred=deferred_mask)
+        if seam:
+            return outputs_class, outputs_mask, attn_mask, outputs_reid, output, side_out
         return outputs_class, outputs_mask, attn_mask, outputs_reid
 
     # ---------------------------------------------------------------------------------------------

@@ -648,13 +648,27 @@ def small_linear(x, weight, bias=None, rows=None, x_add=None, relu=False, residu
     return y if ok else None
 
 
-def small_mlp(x, layers_, in_ln=None, want_normed=False, transpose01=False):
+def __getattr__(name):
+    # `ops.small_seam`: the few-rows seam kernel's wrapper lives with its header's module (seam_ops.py, include/univs_seam_hip.h)
+    if name == "small_seam":
+        from .seam_ops import small_seam
+        return small_seam
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def small_mlp(x, layers_, in_ln=None, want_normed=False, transpose01=False, pre_ln=None, side=None):
     """A chain of up to three 256 -> 256 Linears (ReLU between them as flagged) on a FEW tokens in ONE launch (include/univs_hip.h:
     univs_small_mlp_presplit_f32; csrc/small_linear.hip: small_chain_kernel): the mask-embedding MLP of every prediction head
     (transformer_layers.py:205-217).  `layers_` = [(weight [256, 256], bias [256] | None, relu: bool), ...]; bit-identical to the same
     chain of `small_linear` calls.  `in_ln` = (weight, bias, eps): nn.LayerNorm(256) on the input rows inside the launch (`decoder_norm`,
     ...decoder_univs.py:513); with `want_normed` the normalised rows come back too: (y, x_normed).  `transpose01` as in `small_linear`.
+    `pre_ln` = (residual, weight, bias, eps) / `side` = (weight, bias, add): the end of a decoder layer in the same launch -- the chain runs
+    on x' = layer_norm(x + residual), and side_y = small_linear(x', weight, bias, x_add=add) comes out beside it; the result is then the
+    tuple (y[, x_normed][, x'][, side_y]) (seam_ops.small_mlp_seam, include/univs_seam_hip.h).
     Returns None when not covered (the caller keeps the separate launches)."""
+    if pre_ln is not None or side is not None:
+        from .seam_ops import small_mlp_seam
+        return small_mlp_seam(x, layers_, in_ln=in_ln, want_normed=want_normed, transpose01=transpose01, pre_ln=pre_ln, side=side)
     K = x.shape[-1]
     M = x.numel() // max(K, 1)
     n = len(layers_)

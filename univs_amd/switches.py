@@ -97,6 +97,12 @@ class Switches:
     # csrc/window_attn_qkv.hip) -- no [B, H*W, 3C] tensor; taken where the Linear would run on the three-product kernels (2048 tokens
     # and more).  False: the Linear and the attention as two launches.  Bit-identical either way
     swin_fused_qkv: bool = True
+    # post-norm decoder layer: where one few-rows kernel's output is the next few-rows kernel's only input, both in ONE launch
+    # (seam_ops, csrc/small_linear.hip: small_seam_kernel and the front stages of small_chain_kernel) -- the cross-attention's tail with
+    # the self-attention's packed in-projection, the self-attention's tail with the FFN's linear1 + ReLU, the FFN's LayerNorm with the
+    # prediction head's chain, and the next layer's cross-attention query projection beside that chain: 9 launches per layer instead
+    # of 13.  False: the launch sequence without them.  Bit-identical either way
+    decoder_seams: bool = True
 
 
 SWITCHES = Switches(
@@ -109,7 +115,8 @@ SWITCHES = Switches(
     resident_presplit=_flag("UNIVS_RESIDENT_PRESPLIT", True), small_mlp_chain=_flag("UNIVS_SMALL_MLP_CHAIN", True), fused_proca=_flag("UNIVS_FUSED_PROCA", True),
     fused_sampler=_flag("UNIVS_FUSED_SAMPLER", True), small_mlp_norm=_flag("UNIVS_SMALL_MLP_NORM", True),
     fold_fpn_norm=_flag("UNIVS_FOLD_FPN_NORM", True), fold_attn_merge=_flag("UNIVS_FOLD_ATTN_MERGE", False), swin_channels_last=_flag("UNIVS_SWIN_CHANNELS_LAST", True),
-    encoder_pair=_flag("UNIVS_ENCODER_PAIR", True), swin_fused_qkv=_flag("UNIVS_SWIN_FUSED_QKV", True))
+    encoder_pair=_flag("UNIVS_ENCODER_PAIR", True), swin_fused_qkv=_flag("UNIVS_SWIN_FUSED_QKV", True),
+    decoder_seams=_flag("UNIVS_DECODER_SEAMS", True))
 if SWITCHES.sampler not in ("auto", "reference", "device"):
     raise ValueError(f"UNIVS_SAMPLER={SWITCHES.sampler!r} (expected 'auto', 'reference' or 'device')")
 
