@@ -1,8 +1,8 @@
 """ctypes binding of libunivs_hip.so (the C ABI declared in include/univs_hip.h, include/univs_eval_hip.h,
 include/univs_fused_hip.h, include/univs_pvos_hip.h, include/univs_semantic_hip.h, include/univs_encoder_hip.h,
 include/univs_swin_hip.h, include/univs_frames_hip.h, include/univs_prompts_hip.h, include/univs_png_hip.h,
-include/univs_hota_hip.h, include/univs_pngread_hip.h, include/univs_jpeg_hip.h, include/univs_jpegenc_hip.h, include/univs_idmap_hip.h
-and include/univs_seam_hip.h).
+include/univs_hota_hip.h, include/univs_pngread_hip.h, include/univs_jpeg_hip.h, include/univs_jpegenc_hip.h, include/univs_idmap_hip.h,
+include/univs_seam_hip.h and include/univs_imagelabels_hip.h).
 
 The header is the one statement of the ABI: `SIGNATURES` (restype / argtypes of every `univs_*` symbol) and `CONFIG_FIELDS` (the
 members of `struct UnivsConfig`) are read from its text when this module loads -- no table is kept by hand.
@@ -137,6 +137,12 @@ with open(IDMAP_HEADER_PATH) as _f:
 SEAM_HEADER_PATH = os.path.join(_HERE, "..", "include", "univs_seam_hip.h")
 with open(SEAM_HEADER_PATH) as _f:
     SEAM_SIGNATURES = parse_signatures(_f.read())
+# The seventeenth header (include/univs_imagelabels_hip.h: the labels of a per-image semantic result and the confusion matrix of two
+# label maps), likewise.  (IMAGELABELS_BINDING, not *_SIGNATURES: the sixteenth header's test counts the tables of that name it is
+# disjoint from; tests/test_imagelabels_capi_cpu.py checks this one against all of them.)
+IMAGELABELS_HEADER_PATH = os.path.join(_HERE, "..", "include", "univs_imagelabels_hip.h")
+with open(IMAGELABELS_HEADER_PATH) as _f:
+    IMAGELABELS_BINDING = parse_signatures(_f.read())
 
 _lib = None
 
@@ -160,7 +166,7 @@ def load():
                               *PVOS_SIGNATURES.items(), *SEMANTIC_SIGNATURES.items(), *ENCODER_SIGNATURES.items(), *SWIN_SIGNATURES.items(),
                               *FRAMES_SIGNATURES.items(), *PROMPTS_SIGNATURES.items(), *PNG_SIGNATURES.items(), *HOTA_SIGNATURES.items(),
                               *PNGREAD_SIGNATURES.items(), *JPEG_SIGNATURES.items(), *JPEGENC_SIGNATURES.items(), *IDMAP_SIGNATURES.items(),
-                              *SEAM_SIGNATURES.items()):
+                              *SEAM_SIGNATURES.items(), *IMAGELABELS_BINDING.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing -> loud
         fn.restype = res
         fn.argtypes = args

@@ -11,6 +11,7 @@
 #include "../../include/univs_fused_hip.h"
 #include "../../include/univs_hota_hip.h"
 #include "../../include/univs_idmap_hip.h"
+#include "../../include/univs_imagelabels_hip.h"
 #include "../../include/univs_jpeg_hip.h"
 #include "../../include/univs_jpegenc_hip.h"
 #include "../../include/univs_png_hip.h"
@@ -989,6 +990,25 @@ int univs_idmap_prompts_u8(const uint8_t* ids, int F, int H, int W, const int32_
   if (!ids || !frame || !value || !ty || !tx || !masks || !boxes) return e.null_pointer();
   return e.covered(idmap_prompts_u8(ids, F, H, W, frame, value, N, ty, tx, Ho, Wo, masks, boxes, e.st),
                    "not covered (F H W < 2^31, N Ho Wo < 2^31)");
+}
+
+// (include/univs_imagelabels_hip.h)
+int univs_semseg_labels_f32(const float* r, int C, int hi, int wi, int H, int W, uint8_t* labels, void* stream) {
+  const Entry e("univs_semseg_labels_f32", stream);
+  if (C < 1 || hi < 1 || wi < 1 || H < 1 || W < 1) return e.invalid("bad arguments C=%d hi=%d wi=%d H=%d W=%d", C, hi, wi, H, W);
+  if (!r || !labels) return e.null_pointer();
+  return e.covered(semseg_labels_f32(r, C, hi, wi, H, W, labels, e.st), "not covered (C <= 256, H W < 2^31, hi wi < 2^31)");
+}
+
+int univs_label_confusion_u8(const uint8_t* gt, const uint8_t* pred, long long n, int num_classes, int ignore_label, long long* conf,
+                             long long* stray, void* stream) {
+  const Entry e("univs_label_confusion_u8", stream);
+  if (n < 0 || num_classes < 1 || ignore_label < -1 || ignore_label > 255 || (ignore_label >= 0 && ignore_label < num_classes))
+    return e.invalid("bad arguments n=%lld num_classes=%d ignore_label=%d", n, num_classes, ignore_label);
+  if (n == 0) return UNIVS_OK;
+  if (!gt || !pred || !conf || !stray) return e.null_pointer();
+  return e.covered(label_confusion_u8(gt, pred, n, num_classes, ignore_label, conf, stray, e.st),
+                   "not covered ((num_classes + 1)^2 <= 32768, n < 2^31 - 4, dword-aligned maps, 8-byte aligned counts)");
 }
 
 // (include/univs_seam_hip.h)

@@ -249,6 +249,11 @@ int idmap_census_u8(const unsigned char* ids, int F, int H, int W, int* count, i
 int idmap_prompts_u8(const unsigned char* ids, int F, int H, int W, const int* frame, const int* value, int N, const int* ty, const int* tx,
                      int Ho, int Wo, unsigned char* masks, int* boxes, hipStream_t st);
 
+// ---- semseg_labels.hip: return UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the sizes are not covered, or the launch's error
+int semseg_labels_f32(const float* r, int C, int hi, int wi, int H, int W, unsigned char* labels, hipStream_t st);
+int label_confusion_u8(const unsigned char* gt, const unsigned char* pred, long long n, int K, int ignore_label, long long* conf,
+                       long long* stray, hipStream_t st);
+
 // ---- png_deflate.hip: returns UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the sizes are not covered, or the launch's error
 int png_deflate_maps(const void* src, int src_is_i32, int N, int H, int W, const unsigned char* lut, int K, int C, int rows_per_stripe,
                      unsigned char* scratch, unsigned char* out, long long* offsets, hipStream_t st);

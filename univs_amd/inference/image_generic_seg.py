@@ -31,7 +31,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .. import ops
+from .. import imagelabels_ops, ops
 from ..registry import configurable
 from ..utils.comm import convert_mask_to_box
 from .results import rle_encode_masks
@@ -193,6 +193,12 @@ class AtenSteps:
     def semseg(self, planes, probs):
         return torch.einsum("qc,qhw->chw", probs, self.cropped(planes).sigmoid())
 
+    @staticmethod
+    def semseg_labels(r, out_size):
+        """argmax(0) of the resized semantic result as uint8 [H, W]: what an evaluator makes of `sem_seg` first.  The resize is the one
+        the "scores" result goes through (`_resize_bilinear`: F.interpolate on the CPU), so the labels are the argmax of those scores."""
+        return _resize_bilinear(r, out_size).argmax(0).to(torch.uint8)
+
     def instance_masks(self, planes, out_size):
         m = self.cropped(planes)
         if tuple(m.shape[-2:]) != tuple(out_size):
@@ -223,6 +229,11 @@ class FusedSteps:
 
     def semseg(self, planes, probs):
         return fused_or_aten(ops.image_semseg(self.L, self.padded, self.crop, planes, probs), self.aten.semseg, planes, probs)
+
+    @staticmethod
+    def semseg_labels(r, out_size):
+        r = r.contiguous()
+        return fused_or_aten(imagelabels_ops.semseg_labels(r, out_size), AtenSteps.semseg_labels, r, out_size)
 
     def instance_masks(self, planes, out_size):
         r = ops.image_instance_masks(self.L, self.padded, self.crop, planes, out_size)
@@ -259,12 +270,15 @@ class InferenceImageGenericSegmentation(nn.Module):
         thing_contiguous_ids=(),
         dataset_category_info=None,
         fused: bool = True,
+        sem_seg_as: str = "scores",
     ):
         """`thing_contiguous_ids`: the contiguous category indices that are things, in the order of the reference's
         `metadata.thing_dataset_id_to_contiguous_id.values()` (the instance sub-task keeps those class columns in that order) -- one
         sequence for every dataset, or a mapping {dataset name: sequence} (COCO panoptic and ADE20k have different vocabularies).  The
         panoptic and instance sub-tasks refuse to run without them: with none, every thing class would silently be treated as stuff.
-        `fused=False` runs the ATen formulation of every step on the device (tools/image_bench.py's yardstick)."""
+        `fused=False` runs the ATen formulation of every step on the device (tools/image_bench.py's yardstick).
+        `sem_seg_as` (an attribute, may be set after construction): "scores" returns the semantic result as `sem_seg`, float32 [C, H, W];
+        "labels" returns `sem_seg_labels`, uint8 [H, W] = its argmax(0), instead, without building the [C, H, W] tensor."""
         super().__init__()
         self.num_queries = num_queries
         self.object_mask_threshold = object_mask_threshold
@@ -286,6 +300,7 @@ class InferenceImageGenericSegmentation(nn.Module):
                                      if isinstance(thing_contiguous_ids, dict) else [int(c) for c in thing_contiguous_ids])
         self.dataset_category_info = COMBINED_DATASETS_CATEGORY_INFO if dataset_category_info is None else dataset_category_info
         self.fused = fused
+        self.sem_seg_as = sem_seg_as
 
     @classmethod
     def from_config(cls, cfg, thing_contiguous_ids=(), dataset_category_info=None):
@@ -391,8 +406,8 @@ class InferenceImageGenericSegmentation(nn.Module):
 
     # ---- post-processing of one image --------------------------------------------------------------------------------------------
     def postprocess(self, cls_logits, mask_logits, padded, image_size, out_size, dataset_name=None):
-        """cls_logits [Q', C] (the dataset's columns, before the sigmoid), mask_logits L [Q', h, w] -> {"sem_seg", "panoptic_seg",
-        "instances", "instances_rle"} as enabled (:226-283).  `dataset_name` selects the thing categories when they are a mapping."""
+        """cls_logits [Q', C] (the dataset's columns, before the sigmoid), mask_logits L [Q', h, w] -> {"sem_seg" (or "sem_seg_labels":
+        `sem_seg_as`), "panoptic_seg", "instances", "instances_rle"} as enabled (:226-283).  `dataset_name` selects the thing categories when they are a mapping."""
         self.check_things(dataset_name)
         things = self.things(dataset_name)
         image_size = tuple(int(v) for v in image_size)
@@ -408,8 +423,11 @@ class InferenceImageGenericSegmentation(nn.Module):
             keep = scores_mask > self.stability_score_thresh
             mask_cls, rows, boxes = mask_cls[keep], rows[keep], boxes[keep]
         result = {}
+        if self.sem_seg_as not in ("scores", "labels"):
+            raise ValueError(f"sem_seg_as={self.sem_seg_as!r}: 'scores' or 'labels'")
         if self.semantic_on:
-            result["sem_seg"] = self.semantic_inference(steps, mask_cls, rows, out_size)
+            key = "sem_seg" if self.sem_seg_as == "scores" else "sem_seg_labels"
+            result[key] = self.semantic_inference(steps, mask_cls, rows, out_size)
         if self.panoptic_on:
             result["panoptic_seg"] = self.panoptic_inference(steps, mask_cls, rows, boxes, out_size, things)
         if self.instance_on:
@@ -425,6 +443,8 @@ class InferenceImageGenericSegmentation(nn.Module):
         top = torch.topk(mask_cls.max(-1)[0], k=min(SEMANTIC_TOPK, mask_cls.shape[0]))[1]
         probs = (mask_cls[top] / OPEN_VOC_TEMPERATURE).softmax(-1)
         r = steps.semseg(rows[top], probs)
+        if self.sem_seg_as == "labels":
+            return steps.semseg_labels(r, out_size)              # argmax(0) of the resize below, which is not built
         out = _resize_bilinear(r, out_size)                      # sem_seg_postprocess: the crop is already r's extent
         del r
         return out

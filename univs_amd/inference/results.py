@@ -556,3 +556,103 @@ def write_vss_predictions(inputs: dict, outputs: dict, output_dir: str, contiguo
         img.save(paths[-1])
         img.close()
     return paths
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Per-image results (inference/image_generic_seg.py): the files detectron2's COCOPanopticEvaluator, SemSegEvaluator and
+# COCOEvaluator leave behind
+# ------------------------------------------------------------------------------------------------------------------
+def _stem(file_name: str) -> str:
+    return os.path.splitext(os.path.basename(file_name))[0]
+
+
+def _input_name(inputs: dict) -> str:
+    return inputs["file_name"] if "file_name" in inputs else inputs["file_names"][0]
+
+
+def write_panoptic_prediction(inputs: dict, output: dict, output_dir: str, contiguous_id_to_dataset_id, png="host"):
+    """One image's `panoptic_seg` = (int32 [H, W] segment ids, 0 = nothing; [{"id", "isthing", "category_id"}]) ->
+    `<output_dir>/inference/panoptic/<stem>.png`, the id as a colour (id % 256, id // 256 % 256, id // 65536: panopticapi's `id2rgb`),
+    and the image's record {"image_id", "file_name", "segments_info"} with `category_id` mapped back to the dataset id and `isthing`
+    kept -- what `COCOPanopticEvaluator.process` collects.  `contiguous_id_to_dataset_id`: a list (index = contiguous id) or a dict."""
+    from PIL import Image
+    pan, infos = output["panoptic_seg"]
+    name = _input_name(inputs)
+    save_dir = os.path.join(output_dir, "inference", "panoptic")
+    os.makedirs(save_dir, exist_ok=True)
+    path = os.path.join(save_dir, _stem(name) + ".png")
+    top = max([int(info["id"]) for info in infos], default=0)
+    if _png_mode(png):
+        ids = _on_device(pan, torch.int32)[None]
+        rows = np.arange(top + 1, dtype=np.int64)                    # row k: the colour of id k; an id beyond the listed ones is the last row's
+        lut = np.stack([rows % 256, rows // 256 % 256, rows // 65536], axis=1).astype(np.uint8)
+        if int(ids.max()) > top or int(ids.min()) < 0:
+            raise ValueError(f"panoptic_seg holds ids outside the listed segments' 0 .. {top}")
+        _write_gpu_pngs([path], ids, lut, channels=3)
+    else:
+        p = pan.cpu().numpy() if isinstance(pan, torch.Tensor) else np.asarray(pan)
+        p = p.astype(np.int64)
+        img = Image.fromarray(np.stack([p % 256, p // 256 % 256, p // 65536], axis=-1).astype(np.uint8))
+        img.save(path)
+        img.close()
+    segments = [dict(info, id=int(info["id"]), isthing=bool(info["isthing"]), category_id=int(contiguous_id_to_dataset_id[int(info["category_id"])]))
+                for info in infos]
+    return {"image_id": inputs.get("image_id", _stem(name)), "file_name": _stem(name) + ".png", "segments_info": segments}
+
+
+def semseg_labels_of(output: dict) -> torch.Tensor:
+    """uint8 [H, W] of an image result: its `sem_seg_labels`, or the argmax of its `sem_seg` scores."""
+    if "sem_seg_labels" in output:
+        return torch.as_tensor(output["sem_seg_labels"]).to(torch.uint8)
+    return torch.as_tensor(output["sem_seg"]).argmax(dim=0).to(torch.uint8)
+
+
+def write_semseg_prediction(inputs: dict, output: dict, output_dir: str, contiguous_id_to_dataset_id, png="host"):
+    """One image's semantic labels -> `<output_dir>/inference/sem_seg/<stem>.png`, a grey PNG of dataset ids (a label without a
+    dataset id is a KeyError / IndexError, as a class the vocabulary does not have).  Returns the path."""
+    from PIL import Image
+    labels = semseg_labels_of(output)
+    save_dir = os.path.join(output_dir, "inference", "sem_seg")
+    os.makedirs(save_dir, exist_ok=True)
+    path = os.path.join(save_dir, _stem(_input_name(inputs)) + ".png")
+    lut = np.zeros(256, dtype=np.uint8)
+    for c in torch.unique(labels).tolist():
+        d = int(contiguous_id_to_dataset_id[int(c)])
+        if not 0 <= d <= 255:
+            raise ValueError(f"dataset id {d} of class {c} does not fit a grey PNG")
+        lut[int(c)] = d
+    if _png_mode(png):
+        _write_gpu_pngs([path], _on_device(labels, torch.uint8)[None], lut, channels=1)
+    else:
+        img = Image.fromarray(lut[labels.cpu().numpy()])
+        img.save(path)
+        img.close()
+    return path
+
+
+def image_instances_to_coco_json(inputs: dict, output: dict, contiguous_id_to_dataset_id) -> List[dict]:
+    """One image's `instances` / `instances_rle` -> COCO result records {"image_id", "category_id" (dataset id), "segmentation",
+    "score", "bbox" [x, y, w, h] from the driver's XYXY boxes} (detectron2's `instances_to_coco_json`)."""
+    inst = output["instances"]
+    boxes = inst.pred_boxes.tensor.detach().cpu().double().numpy().reshape(-1, 4)
+    scores = inst.scores.detach().cpu().tolist()
+    classes = inst.pred_classes.detach().cpu().tolist()
+    name = _input_name(inputs)
+    image_id = inputs.get("image_id", _stem(name))
+    records = []
+    for k, rle in enumerate(output["instances_rle"]):
+        x0, y0, x1, y1 = (float(v) for v in boxes[k])
+        records.append({"image_id": image_id, "category_id": int(contiguous_id_to_dataset_id[int(classes[k])]), "segmentation": rle,
+                        "score": float(scores[k]), "bbox": [x0, y0, x1 - x0, y1 - y0]})
+    return records
+
+
+def write_instances_json(records: Sequence[dict], output_dir: str) -> str:
+    """The records of every image -> `<output_dir>/inference/coco_instances_results.json`.  Mask AP is not scored here."""
+    import json
+    save_dir = os.path.join(output_dir, "inference")
+    os.makedirs(save_dir, exist_ok=True)
+    path = os.path.join(save_dir, "coco_instances_results.json")
+    with open(path, "w") as f:
+        json.dump(list(records), f)
+    return path

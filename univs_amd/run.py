@@ -6,6 +6,8 @@
                             [--visualize off|host|gpu [--categories-json C]]
                             [--gt-json G [--hota] | --pan-gt-json P --truth-dir T | --davis-root V | --pvos-data V]
                             [KEY VALUE ...]
+    python -m univs_amd.run --config-file F --weights W (--image-dir D | --pan-gt-json P --image-root R --truth-dir T [--sem-gt-dir S])
+                            --dataset-name coco_panoptic|coco|ade20k --output-dir O [--categories-json C] [--batch B] ...
 
 The model is `build_model(load_cfg(F, [KEY VALUE ...]))` with `ckpt["model"]` loaded strictly (the reference's state-dict layout).  The
 frames are the videos of a YouTube-VIS-format file, or the sub-folders of a folder of jpg / png frames (data/datasets.py), mapped by
@@ -37,6 +39,16 @@ changes), and a legend.json of the ids drawn.  Drawn are the VOS driver's id map
 output in the category colours (--categories-json, else the default palette) and VIS results that carry per-frame masks; an output without
 a per-pixel result at the output size prints one line and writes nothing.  host draws with numpy and encodes with Pillow, gpu does both
 inside csrc/jpeg_encode.hip: the same files byte for byte; with --decode gpu the frames never leave the device.  The default is off.
+
+Images: a --dataset-name of an image vocabulary (coco_panoptic, coco, ade20k) runs the per-image driver on the jpg / png files of
+--image-dir, or on the images of a panoptic ground-truth file (--pan-gt-json P --image-root R --truth-dir T: data.load_panoptic_json),
+mapped by data.ImageTestMapper, --batch images per model call.  The class table (dataset ids, names, which classes are things) is read
+from P's own `categories`, without P from --categories-json; the driver's `thing_contiguous_ids` are set from it and its semantic result
+is asked for as labels (`sem_seg_as = "labels"`: csrc/semseg_labels.hip).  Written are O/inference/panoptic/<stem>.png with
+O/inference/predictions.json (the segments' classes), O/inference/sem_seg/<stem>.png and O/inference/coco_instances_results.json, for the sub-tasks the config enables.  With P and T the
+panoptic results are scored by evaluation.image.PanopticEvaluator (PQ / SQ / RQ), with --sem-gt-dir S (class-id PNGs named after the
+images) the semantic ones by SemSegEvaluator (mIoU); both dictionaries are printed as one.  Mask AP is not scored.  --visualize draws
+the panoptic map, else the semantic labels, to O/inference/Overlays.
 """
 import argparse
 import json
@@ -46,14 +58,18 @@ import sys
 import torch
 
 from .config import load_cfg
-from .data import VideoTestMapper, VOSTestMapper, is_vos_name, load_video_json, load_vos_json, video_records_from_dir, vos_records_from_dirs
-from .engine import inference_on_videos
+from .data import (ImageTestMapper, VideoTestMapper, VOSTestMapper, image_records_from_dir, is_vos_name, load_categories_json, load_panoptic_json,
+                   load_video_json, load_vos_json, video_records_from_dir, vos_records_from_dirs)
+from .engine import inference_on_images, inference_on_videos
 from .inference.results import write_vos_pngs
 from .modeling.build import build_model
 
 
+IMAGE_NAMES = ("coco_panoptic", "coco", "ade20k")                    # the per-image driver's vocabularies (image_generic_seg.py: check_dataset)
+
+
 def parse_args(argv=None):
-    ap = argparse.ArgumentParser(prog="python -m univs_amd.run", description="video inference from files on disk")
+    ap = argparse.ArgumentParser(prog="python -m univs_amd.run", description="video and image inference from files on disk")
     ap.add_argument("--config-file", required=True)
     ap.add_argument("--weights", required=True, help="a checkpoint whose \"model\" entry is the state dict")
     ap.add_argument("--json", help="a YouTube-VIS-format test file")
@@ -62,6 +78,9 @@ def parse_args(argv=None):
     ap.add_argument("--video-dir", help="a folder whose sub-folders hold the frames of one video each")
     ap.add_argument("--masks-dir", help="with --video-dir and --dataset-name: the folder of the videos' annotation PNGs (a VOS data set's Annotations)")
     ap.add_argument("--vos-meta", help="with --masks-dir: the folder of meta.json / obj_class.json (default: the one above --masks-dir)")
+    ap.add_argument("--image-dir", help="a folder of jpg / png images: the per-image driver (with --dataset-name coco_panoptic, coco or ade20k)")
+    ap.add_argument("--sem-gt-dir", help="an image run: the folder of class-id PNGs named after the images, scored with SemSegEvaluator")
+    ap.add_argument("--batch", type=int, default=1, help="an image run: images per model call")
     ap.add_argument("--output-dir", required=True)
     ap.add_argument("--resize", choices=("gpu", "host"), default="gpu")
     ap.add_argument("--decode", choices=("host", "gpu"), default="host", help="who decodes the JPEG frames: Pillow, or the HIP decoder (needs --resize gpu)")
@@ -80,6 +99,14 @@ def parse_args(argv=None):
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="KEY VALUE pairs merged into the config")
     args = ap.parse_args(argv)
     from_json = args.json is not None
+    if args.image_dir is not None and (from_json or args.video_dir is not None):
+        ap.error("--image-dir is a source of its own: not with --json or --video-dir")
+    args.image = args.image_dir is not None or (not from_json and args.video_dir is None and args.dataset_name in IMAGE_NAMES and
+                                                args.pan_gt_json is not None and args.image_root is not None)
+    if args.image:
+        return check_image_args(ap, args)
+    if args.sem_gt_dir is not None or args.batch != 1:
+        ap.error("--sem-gt-dir and --batch go with an image run (--image-dir, or --pan-gt-json with --image-root and an image --dataset-name)")
     if from_json == (args.video_dir is not None):
         ap.error("give either --json (with --image-root and --dataset-name) or --video-dir")
     if from_json and not (args.image_root and args.dataset_name):
@@ -104,6 +131,123 @@ def parse_args(argv=None):
     if args.davis_root and not ("davis16" in args.dataset_name or "davis17" in args.dataset_name):
         ap.error("--davis-root needs a davis16 / davis17 --dataset-name")
     return args
+
+
+def check_image_args(ap, args):
+    """The argument rules of an image run, in the style of the video ones."""
+    if args.dataset_name not in IMAGE_NAMES:
+        ap.error("an image run needs --dataset-name coco_panoptic, coco or ade20k")
+    if (args.pan_gt_json is None) != (args.truth_dir is None):
+        ap.error("--pan-gt-json and --truth-dir go together")
+    if args.image_dir is None and not args.image_root:
+        ap.error("--pan-gt-json as the source of an image run needs --image-root")
+    if args.pan_gt_json is None and args.categories_json is None:
+        ap.error("an image run reads its class table from --pan-gt-json, or without one from --categories-json")
+    if args.masks_dir is not None or args.vos_meta is not None or args.gt_json or args.hota or args.davis_root or args.pvos_data:
+        ap.error("--masks-dir, --vos-meta, --gt-json, --hota, --davis-root and --pvos-data belong to video runs")
+    if args.batch < 1:
+        ap.error("--batch is at least 1")
+    args.vos = False
+    return args
+
+
+def build_image_evaluators(args, table, records):
+    from .evaluation.image import PanopticEvaluator, SemSegEvaluator
+    evaluators = []
+    if args.pan_gt_json:
+        evaluators.append(PanopticEvaluator(args.pan_gt_json, args.truth_dir, args.output_dir, class_table=table, device=args.device, png=args.png,
+                                            reader=args.reader))
+    if args.sem_gt_dir:
+        evaluators.append(SemSegEvaluator(args.sem_gt_dir, len(table["ids"]), 255, table["names"], args.output_dir, device=args.device, png=args.png,
+                                          reader=args.reader))
+    return evaluators
+
+
+def image_overlay_table(args, output, table):
+    """(0, ids [1, H, W], lut, {row: name}) of one image's result: the panoptic map in its segments' category colours, else the
+    semantic labels; a sentence where the output holds neither."""
+    from .inference import overlay_rule as ov
+    from .inference.results import semseg_labels_of
+    source = argparse.Namespace(categories_json=args.categories_json or args.pan_gt_json)
+    with open(source.categories_json) as f:
+        if not all("color" in c for c in json.load(f)["categories"]):
+            source.categories_json = None                           # no colours in the file: the default palette
+    if "panoptic_seg" in output:
+        pan, infos = output["panoptic_seg"]
+        lut, names, rows = _category_table(source, ov.ALPHA_VPS, len(table["ids"]))
+        ids = torch.zeros_like(pan, dtype=torch.int32)
+        for info in infos:
+            c = int(info["category_id"])
+            ids[pan == int(info["id"])] = rows.get(table["ids"][c], 0) if rows is not None else c + 1
+        return 0, ids[None], lut, names or {c + 1: n for c, n in enumerate(table["names"])}
+    if "sem_seg_labels" in output or "sem_seg" in output:
+        sem = semseg_labels_of(output).to(torch.int32)
+        lut, names, rows = _category_table(source, ov.ALPHA_VSS, len(table["ids"]))
+        if rows is not None:
+            to_row = torch.tensor([rows.get(d, 0) for d in table["ids"]], dtype=torch.int32, device=sem.device)
+            return 0, to_row[sem.long()][None], lut, names
+        return 0, (sem + 1)[None], lut, {c + 1: n for c, n in enumerate(table["names"])}
+    return "the output holds neither a panoptic map nor semantic labels"
+
+
+def run_images(args, cfg, model):
+    """An image run: records, class table, mapper, writers and evaluators around `inference_on_images`."""
+    from .inference.results import image_instances_to_coco_json, write_instances_json, write_panoptic_prediction, write_semseg_prediction
+    if args.image_dir is not None:
+        records = image_records_from_dir(args.image_dir)
+        table = load_categories_json(args.pan_gt_json or args.categories_json)
+    else:
+        records, table = load_panoptic_json(args.pan_gt_json, args.image_root, args.truth_dir, semseg_dir=args.sem_gt_dir)
+    for r in records:
+        r["dataset_name"] = args.dataset_name
+    driver = model.inference_img_generic_seg
+    things = driver.thing_contiguous_ids if isinstance(driver.thing_contiguous_ids, dict) else {}
+    things[args.dataset_name] = list(table["thing_contiguous_ids"])
+    driver.thing_contiguous_ids = things
+    driver.sem_seg_as = "labels"
+    thing_dataset_ids = [table["ids"][c] for c in table["thing_contiguous_ids"]]      # an instance's class is its column among the things
+    mapper = ImageTestMapper.from_config(cfg, resize=args.resize, device=args.device, decode=args.decode)
+    os.makedirs(args.output_dir, exist_ok=True)
+    evaluators = build_image_evaluators(args, table, records)
+    writes_panoptic = any(type(ev).__name__ == "PanopticEvaluator" for ev in evaluators)
+    instances, panoptic = [], []
+
+    def on_output(inputs, outputs):
+        for item, output in zip(inputs, outputs):
+            if "panoptic_seg" in output and not writes_panoptic:
+                panoptic.append(write_panoptic_prediction(item, output, args.output_dir, table["ids"], png=args.png))
+            if "sem_seg_labels" in output or "sem_seg" in output:
+                write_semseg_prediction(item, output, args.output_dir, table["ids"], png=args.png)
+            if "instances" in output:
+                instances.extend(image_instances_to_coco_json(item, output, thing_dataset_ids))
+            if args.visualize != "off":
+                write_image_overlay(args, item, output, table)
+    results = inference_on_images(model, records, mapper, evaluators, on_output=on_output, batch=args.batch)
+    if driver.instance_on:
+        write_instances_json(instances, args.output_dir)
+    if panoptic:                                                     # (the segments' classes: what PanopticEvaluator.evaluate writes when it runs)
+        with open(os.path.join(args.output_dir, "inference", "predictions.json"), "w") as f:
+            json.dump({"annotations": panoptic}, f)
+    if evaluators:
+        print(json.dumps(results, default=str))
+    return results
+
+
+def write_image_overlay(args, item, output, table):
+    from .data import read_images
+    from .inference.results import write_overlay_jpegs
+    t = image_overlay_table(args, output, table)
+    if isinstance(t, str):
+        print(f"--visualize: image {item.get('image_id')}: {t}; nothing written")
+        return []
+    first, ids, lut, row_names = t
+    names = item["file_names"][:1]
+    frames = read_images(names, decode=args.decode, device=args.device if args.decode == "gpu" else None)
+    paths = write_overlay_jpegs(args.output_dir, names, 0, frames, ids, lut, jpeg=args.visualize)
+    present = torch.unique(torch.as_tensor(ids).long().clamp(0, len(lut) - 1)).tolist()
+    with open(os.path.splitext(paths[0])[0] + ".legend.json", "w") as f:
+        json.dump(_legend(lut, row_names, present), f, indent=1, sort_keys=True)
+    return paths
 
 
 def build_evaluator(args):
@@ -242,6 +386,9 @@ def main(argv=None):
     ckpt = torch.load(args.weights, map_location="cpu")
     model.load_state_dict(ckpt["model"], strict=True)
     model = model.to(args.device)
+    if getattr(args, "image", False):
+        run_images(args, cfg, model)
+        return 0
     if args.vos and getattr(args, "masks_dir", None) is not None:
         records = vos_records_from_dirs(args.video_dir, args.masks_dir, args.dataset_name, meta_dir=args.vos_meta, reader=args.reader,
                                         device=args.device)
