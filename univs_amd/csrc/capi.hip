@@ -21,6 +21,7 @@
 #include "../../include/univs_seam_hip.h"
 #include "../../include/univs_semantic_hip.h"
 #include "../../include/univs_swin_hip.h"
+#include "../../include/univs_text_hip.h"
 #include "common.h"
 #include "config.h"
 #include "launchers.h"
@@ -1009,6 +1010,18 @@ int univs_label_confusion_u8(const uint8_t* gt, const uint8_t* pred, long long n
   if (!gt || !pred || !conf || !stray) return e.null_pointer();
   return e.covered(label_confusion_u8(gt, pred, n, num_classes, ignore_label, conf, stray, e.st),
                    "not covered ((num_classes + 1)^2 <= 32768, n < 2^31 - 4, dword-aligned maps, 8-byte aligned counts)");
+}
+
+// (include/univs_text_hip.h)
+int univs_text_attention_f32(const float* qkv, const int* start, int S, long long Ntok, int E, int heads, int Lmax, float scale, float* out,
+                             void* stream) {
+  const Entry e("univs_text_attention_f32", stream);
+  if (S < 0 || Ntok < 0 || E < 1 || heads < 1 || E % heads != 0 || Lmax < 1)
+    return e.invalid("bad arguments S=%d Ntok=%lld E=%d heads=%d Lmax=%d", S, Ntok, E, heads, Lmax);
+  if (S == 0 || Ntok == 0) return UNIVS_OK;
+  if (!qkv || !start || !out) return e.null_pointer();
+  return e.covered(text_attention_f32(qkv, start, S, Ntok, E, heads, Lmax, scale, out, e.st),
+                   "not covered (E / heads in {16, 32, 64}, Lmax <= 128, Ntok 3 E < 2^31, S heads < 2^31)");
 }
 
 // (include/univs_seam_hip.h)

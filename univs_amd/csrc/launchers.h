@@ -254,6 +254,10 @@ int semseg_labels_f32(const float* r, int C, int hi, int wi, int H, int W, unsig
 int label_confusion_u8(const unsigned char* gt, const unsigned char* pred, long long n, int K, int ignore_label, long long* conf,
                        long long* stray, hipStream_t st);
 
+// ---- text_attn.hip: returns UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the sizes are not covered, or the launch's error
+int text_attention_f32(const float* qkv, const int* start, int S, long long Ntok, int E, int heads, int Lmax, float scale, float* out,
+                       hipStream_t st);
+
 // ---- png_deflate.hip: returns UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the sizes are not covered, or the launch's error
 int png_deflate_maps(const void* src, int src_is_i32, int N, int H, int W, const unsigned char* lut, int K, int C, int rows_per_stripe,
                      unsigned char* scratch, unsigned char* out, long long* offsets, hipStream_t st);

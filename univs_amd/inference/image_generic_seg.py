@@ -349,7 +349,8 @@ class InferenceImageGenericSegmentation(nn.Module):
             raise NotImplementedError(
                 f"per-image evaluation of {dataset_name!r}: no class vocabulary of that name (image datasets are named after theirs: "
                 f"'coco_panoptic', 'coco', 'ade20k')")
-        if not (dataset_name.startswith("coco") or dataset_name.startswith("ade20k")):
+        if not (dataset_name.startswith("coco") or dataset_name.startswith("ade20k")
+                or dataset_name in getattr(self, "installed_vocabularies", ())):          # (vocabulary.install)
             raise ValueError(f"do not support the model inference on {dataset_name}.")
         if self.sem_seg_postprocess_before_inference:
             raise NotImplementedError("MODEL.MASK_FORMER.TEST.SEM_SEG_POSTPROCESSING_BEFORE_INFERENCE True is not built")

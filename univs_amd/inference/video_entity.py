@@ -451,6 +451,15 @@ class InferenceVideoEntity(nn.Module):
             targets = model.prepare_targets.process_inference(batched_inputs, tuple(images.tensor.shape[-2:]), self.device,
                                                               getattr(model, "text_prompt_encoder", None),
                                                               images.image_sizes[0])
+        installed = getattr(self, "installed_vocabularies", {}).get(targets[0]["dataset_name"])   # (vocabulary.install)
+        if installed is not None:
+            # a vocabulary made from names: its own sub-task and its own thing categories, for this call only
+            targets[0]["sub_task"] = installed["sub_task"]
+            named_things, self.thing_dataset_ids = self.thing_dataset_ids, installed["thing_dataset_ids"]
+            try:
+                return self.inference_video(model, batched_inputs, images, targets)
+            finally:
+                self.thing_dataset_ids = named_things
         if self.video_unified_inference_entities:
             targets[0]["sub_task"] = self.video_unified_inference_entities
         else:

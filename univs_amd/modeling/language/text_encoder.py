@@ -97,6 +97,83 @@ class CLIPLangEncoder(nn.Module):
         x_word = (h.reshape(L * N, -1) @ self.text_projection).view(L, N, -1).transpose(0, 1)
         return x_word, x_eot
 
+    def kept_lengths(self, text, word_rows=None):
+        """Tokens the ragged tower keeps per text, a list of N ints: up to and including the end-of-text token (`argmax + 1`, the dense
+        path's rule -- also for a text cut at the context length that holds no end-of-text token), all of them for the `word_rows`.
+        Computed where `text` lies: a host tensor costs no synchronisation, a device tensor one download."""
+        lengths = (text.argmax(dim=-1) + 1).tolist()
+        for r in (word_rows or ()):
+            lengths[r] = self.context_length
+        return lengths
+
+    @torch.no_grad()
+    @fp32_region
+    def encode_text_ragged(self, text: torch.Tensor, only_eot: bool = True, word_rows=None, lengths=None):
+        """`encode_text` on the tokens that matter only.  The attention is causal, so the feature at a text's end-of-text token depends
+        on the tokens up to it and on nothing behind: every text is cut there (`kept_lengths`), the kept tokens of all texts are packed
+        into [Ntok, E] rows, and the tower runs on those -- Linears and LayerNorms per row, the attention per sequence
+        (text_ops.varlen_causal_attention, csrc/text_attn.hip; no [N, h, 77, 77] scores).  `ln_final` and `text_projection` see the
+        end-of-text rows and the `word_rows` only.
+        text: int64 [N, context_length] on any device; word_rows: the texts whose per-token features are consumed (they keep all their
+        tokens); lengths: `kept_lengths(text, word_rows)` where the caller already has it.
+        -> x_eot [N, embed_dim]  (and x_word [len(word_rows), context_length, embed_dim] first when only_eot=False).
+        The same numbers as the dense path to fp32 rounding, not bit for bit: the GEMMs see other row counts."""
+        from ... import text_ops
+        from ...layers import linear
+        N, L = text.shape
+        if L != self.context_length:
+            raise ValueError(f"expected {self.context_length} tokens per text, got {L}")
+        word_rows = [int(r) for r in (word_rows or ())]
+        if any(not 0 <= r < N for r in word_rows):
+            raise ValueError(f"word_rows outside the {N} texts")
+        if lengths is None:
+            lengths = self.kept_lengths(text, word_rows)
+        dev = self.device
+        n = torch.as_tensor(lengths, dtype=torch.int64)
+        if n.numel() != N or (N and (int(n.min()) < 1 or int(n.max()) > L)):
+            raise ValueError("lengths: one entry in [1, context_length] per text")
+        start = torch.zeros(N + 1, dtype=torch.int64)
+        torch.cumsum(n, 0, out=start[1:])
+        Ntok, Lmax = int(start[-1]), (int(n.max()) if N else 1)
+        seq = torch.repeat_interleave(torch.arange(N), n)                      # [Ntok] text of a packed row ...
+        pos = torch.arange(Ntok) - start[:-1][seq]                             # ... and its position in it
+        ids = text[seq.to(text.device), pos.to(text.device)].to(dev)
+        pos_dev = pos.to(dev)
+        eot = n - 1                                                            # (a cut text ends at its end-of-text token)
+        if word_rows:
+            wr = torch.as_tensor(word_rows)
+            eot[wr] = text[wr.to(text.device)].argmax(dim=-1).cpu()
+        sel = [start[:-1] + eot]                                               # the rows ln_final sees: N end-of-text rows ...
+        for r in word_rows:                                                    # ... then context_length rows per word text
+            sel.append(int(start[r]) + torch.arange(L))
+        sel = torch.cat(sel).to(dev)
+        start32 = text_ops.check_start(start, Ntok, Lmax)
+        start_dev = start32.to(dev) if dev.type == "cuda" else None
+        blocks = self.transformer.resblocks
+        heads = blocks[0].attn.num_heads if len(blocks) else 1
+
+        def attention(qkv):
+            out = text_ops.varlen_causal_attention(qkv, start32, heads, Lmax, start_dev=start_dev) if qkv.is_cuda else None
+            return out if out is not None else text_ops.varlen_causal_attention_aten(qkv, start32, heads, Lmax)
+        # x <- emb + pos ; h = ln_1(x) of the first block
+        first_norm = blocks[0].ln_1 if len(blocks) else self.ln_final
+        x, h = layer_norm(first_norm, self.token_embedding(ids), residual=self.positional_embedding[pos_dev], return_sum=True)
+        for i, blk in enumerate(blocks):
+            a = attention(linear(h, blk.attn.in_proj_weight, blk.attn.in_proj_bias))
+            a = linear(a, blk.attn.out_proj.weight, blk.attn.out_proj.bias)
+            x, h = layer_norm(blk.ln_2, a, residual=x, return_sum=True)        # x <- x + a ; h = ln_2(x)
+            if i + 1 < len(blocks):
+                x, h = layer_norm(blocks[i + 1].ln_1, blk.mlp(h), residual=x, return_sum=True)
+            else:                                                              # the last MLP and ln_final: the consumed rows only
+                h = layer_norm(self.ln_final, blk.mlp(h[sel]), residual=x[sel])
+        if not len(blocks):
+            h = h[sel]
+        x_eot = h[:N] @ self.text_projection
+        if only_eot:
+            return x_eot
+        x_word = (h[N:] @ self.text_projection).view(len(word_rows), L, self.text_projection.shape[1])   # (no word rows: [0, L, D])
+        return x_word, x_eot
+
 
 CLIP_TEXT_CONFIGS = {
     # RESNETS_DEPTH flag -> (embed_dim, width, heads)           TextEncoder.py:157-173

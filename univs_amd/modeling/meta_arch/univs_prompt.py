@@ -98,14 +98,15 @@ class UniVS_Prompt(nn.Module):
         if self.semantic_extraction_enable:                                              # before everything else (univs_prompt.py:420-421)
             return self._driver("inference_video_semantic_extraction", "semantic extraction").eval(self, batched_inputs)
         name = batched_inputs[0]["dataset_name"]
-        if name.startswith("coco") or name.startswith("ade20k"):
+        installed = getattr(self, "installed_vocabularies", {})                            # (vocabulary.install)
+        if name.startswith("coco") or name.startswith("ade20k") or (name in installed and "image_id" in batched_inputs[0]):
             if self.inference_img_generic_seg is None:
                 raise NotImplementedError("per-image evaluation: this model was built without InferenceImageGenericSegmentation")
             return self.inference_img_generic_seg.eval(self, batched_inputs)             # images (univs_prompt.py:420-426)
         if batched_inputs[0]["task"] in {"grounding", "sot"} or len(self.custom_videos_text):
             return self.inference_video_vos.eval(self, batched_inputs)          # prompt-specified tasks
-        if self.video_unified_inference_enable or self.custom_videos_enable:
-            if name.startswith(("ytvis", "ovis", "vipseg", "vspw")) or self.custom_videos_enable:
+        if self.video_unified_inference_enable or self.custom_videos_enable or name in installed:
+            if name.startswith(("ytvis", "ovis", "vipseg", "vspw")) or self.custom_videos_enable or name in installed:
                 return self.inference_video_entity.eval(self, batched_inputs)   # category-specified tasks
             raise ValueError(f"Not support to eval the dataset {name} yet")
         return self.non_unified_inference(batched_inputs)

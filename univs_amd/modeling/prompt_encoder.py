@@ -119,11 +119,29 @@ class TextPromptEncoder:
         len_word_expressions = [len(exp.split(" ")) + 5 for exp in expressions]
         if tokens is None:
             tokens = pre_tokenize_expression(expressions)
-        tokens = tokens.to(device)
         E, P, L = tokens.shape
-        flat = tokens.reshape(E * P, L)
         words, eots = [], []
-        for lo in range(0, E * P, max_batch):            # bounded activation memory for long expression lists
+        if SWITCHES.text_ragged:
+            # the tower on the kept tokens only (encode_text_ragged); the bare-expression rows keep all their tokens.  A chunk holds
+            # whole texts of at most max_batch x L tokens together: the activation memory `max_batch` stood for on the dense path
+            flat = tokens.reshape(E * P, L)              # (where it lies: the lengths of host tokens cost no synchronisation)
+            lengths = self.lang_encoder.kept_lengths(flat, range(0, E * P, P))
+            lo = 0
+            while lo < E * P:
+                hi, budget = lo + 1, max_batch * L - lengths[lo]
+                while hi < E * P and lengths[hi] <= budget:
+                    budget -= lengths[hi]
+                    hi += 1
+                w, e = self.lang_encoder.encode_text_ragged(flat[lo:hi], only_eot=False, lengths=lengths[lo:hi],
+                                                            word_rows=[i - lo for i in range(lo, hi) if i % P == 0])
+                words.append(w)
+                eots.append(e)
+                lo = hi
+            chunks = ()
+        else:
+            flat = tokens.to(device).reshape(E * P, L)
+            chunks = range(0, E * P, max_batch)          # bounded activation memory for long expression lists
+        for lo in chunks:
             w, e = self.lang_encoder.encode_text(flat[lo:lo + max_batch], only_eot=False)
             first = [i - lo for i in range(lo, min(lo + max_batch, E * P)) if i % P == 0]
             if first:                                    # only the bare-expression rows are consumed per token

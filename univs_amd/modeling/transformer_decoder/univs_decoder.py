@@ -676,8 +676,9 @@ class VideoMultiScaleMaskedTransformerDecoderUniVS(nn.Module):
             batch = []
             for tv in targets:
                 name = tv["dataset_name"]
-                assert name in combined_datasets_category_info
-                num_classes, start_idx = combined_datasets_category_info[name]
+                info = getattr(self, "dataset_category_info", None) or combined_datasets_category_info   # (vocabulary.install)
+                assert name in info
+                num_classes, start_idx = info[name]
                 emb = self.clip_cls_text_emb[start_idx:start_idx + num_classes].to(device)
                 assert len(emb) == num_classes
                 e = self.text2vis_projection(self.text_norm(emb))

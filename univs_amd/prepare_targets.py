@@ -98,8 +98,9 @@ class PrepareTargets:
                 name = tv["dataset_name"]
                 if name in {"flickr"}:
                     raise NotImplementedError("phrase grounding on Flickr (class names from phrases) is not built")
-                if tv.get("is_raw_video", False) or name not in combined_datasets_category_info:
+                info = getattr(self, "dataset_category_info", None) or combined_datasets_category_info   # (vocabulary.install)
+                if tv.get("is_raw_video", False) or name not in info:
                     out["clip_cls_text_emb"] = self.clip_cls_text_emb
                 else:
-                    num_classes, start = combined_datasets_category_info[name]
+                    num_classes, start = info[name]
                     out["clip_cls_text_emb"] = self.clip_cls_text_emb[start:start + num_classes]

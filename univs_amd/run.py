@@ -49,6 +49,14 @@ O/inference/predictions.json (the segments' classes), O/inference/sem_seg/<stem>
 panoptic results are scored by evaluation.image.PanopticEvaluator (PQ / SQ / RQ), with --sem-gt-dir S (class-id PNGs named after the
 images) the semantic ones by SemSegEvaluator (mIoU); both dictionaries are printed as one.  Mask AP is not scored.  --visualize draws
 the panoptic map, else the semantic labels, to O/inference/Overlays.
+
+A vocabulary of one's own: --class-names F (a text file, one name per line, or a json with a `categories` list) with --video-dir or
+--image-dir.  The table is made from the names by the model's own CLIP text tower, or by --clip-weights W where the config builds none
+(univs_amd/vocabulary.py), and installed under --dataset-name (default custom; none of the named vocabularies): the frames of
+--video-dir then run through the unified entity loop under --sub-task vis | vss | vps (default vis; vps needs `isthing` in a json), the
+images of --image-dir through the per-image driver with the class table taken from the vocabulary.  O/inference/vocabulary.json maps
+contiguous id to name; the names reach the overlays' legend.json.  No evaluator runs: no ground truth shares such a vocabulary.
+Without --class-names every run parses, runs and writes as before.
 """
 import argparse
 import json
@@ -96,9 +104,15 @@ def parse_args(argv=None):
     ap.add_argument("--truth-dir", help="the folder of the ground-truth panoptic PNGs")
     ap.add_argument("--davis-root", help="the DAVIS folder (Annotations/, ImageSets/): score a sot_davis* run with DAVISEvaluator")
     ap.add_argument("--pvos-data", help="the VIPOSeg split folder (Annotations/, meta files): score a pvos_* run with PVOSEvaluator")
+    ap.add_argument("--class-names", help="with --video-dir or --image-dir: the class vocabulary of the run, a text file (one name per line) or "
+                                          "a json with a `categories` list; its table is made by the CLIP text tower (univs_amd/vocabulary.py)")
+    ap.add_argument("--clip-weights", help="with --class-names: a converted CLIP text-tower checkpoint, where the config builds no language encoder")
+    ap.add_argument("--sub-task", choices=("vis", "vss", "vps"), help="with --class-names and --video-dir: what the entity loop produces "
+                                                                      "(default vis; vps needs `isthing`, i.e. a categories json)")
     ap.add_argument("opts", nargs=argparse.REMAINDER, help="KEY VALUE pairs merged into the config")
     args = ap.parse_args(argv)
     from_json = args.json is not None
+    check_class_name_args(ap, args)
     if args.image_dir is not None and (from_json or args.video_dir is not None):
         ap.error("--image-dir is a source of its own: not with --json or --video-dir")
     args.image = args.image_dir is not None or (not from_json and args.video_dir is None and args.dataset_name in IMAGE_NAMES and
@@ -133,15 +147,39 @@ def parse_args(argv=None):
     return args
 
 
+def check_class_name_args(ap, args):
+    """The rules of --class-names (a vocabulary made from names; without it nothing here applies)."""
+    if args.class_names is None:
+        if args.clip_weights is not None or args.sub_task is not None:
+            ap.error("--clip-weights and --sub-task go with --class-names")
+        return
+    if args.json is not None:
+        ap.error("--class-names goes with --video-dir or --image-dir, not with --json (a registered data set has its named vocabulary)")
+    if args.masks_dir is not None:
+        ap.error("--class-names is not for a VOS run (--masks-dir): it has no class vocabulary")
+    if args.gt_json or args.pan_gt_json or args.sem_gt_dir or args.davis_root or args.pvos_data:
+        ap.error("--class-names: the ground truth of a registered data set does not share a vocabulary made from names; no evaluator")
+    if args.image_dir is not None and args.sub_task is not None:
+        ap.error("--sub-task chooses what the video entity loop produces; an image run has none")
+    if args.dataset_name is None:
+        args.dataset_name = "custom"
+    if args.dataset_name in IMAGE_NAMES or is_vos_name(args.dataset_name):
+        ap.error("--class-names installs a vocabulary of its own: --dataset-name names it and is none of the named ones (default custom)")
+    if args.sub_task == "vps":
+        from .vocabulary import read_names
+        if not os.path.isfile(args.class_names) or read_names(args.class_names)[1] is None:
+            ap.error("--sub-task vps needs to know which names are things: give --class-names a json whose categories carry `isthing`")
+
+
 def check_image_args(ap, args):
     """The argument rules of an image run, in the style of the video ones."""
-    if args.dataset_name not in IMAGE_NAMES:
-        ap.error("an image run needs --dataset-name coco_panoptic, coco or ade20k")
+    if args.class_names is None and args.dataset_name not in IMAGE_NAMES:
+        ap.error("an image run needs --dataset-name coco_panoptic, coco or ade20k (or --class-names)")
     if (args.pan_gt_json is None) != (args.truth_dir is None):
         ap.error("--pan-gt-json and --truth-dir go together")
     if args.image_dir is None and not args.image_root:
         ap.error("--pan-gt-json as the source of an image run needs --image-root")
-    if args.pan_gt_json is None and args.categories_json is None:
+    if args.class_names is None and args.pan_gt_json is None and args.categories_json is None:
         ap.error("an image run reads its class table from --pan-gt-json, or without one from --categories-json")
     if args.masks_dir is not None or args.vos_meta is not None or args.gt_json or args.hota or args.davis_root or args.pvos_data:
         ap.error("--masks-dir, --vos-meta, --gt-json, --hota, --davis-root and --pvos-data belong to video runs")
@@ -169,9 +207,10 @@ def image_overlay_table(args, output, table):
     from .inference import overlay_rule as ov
     from .inference.results import semseg_labels_of
     source = argparse.Namespace(categories_json=args.categories_json or args.pan_gt_json)
-    with open(source.categories_json) as f:
-        if not all("color" in c for c in json.load(f)["categories"]):
-            source.categories_json = None                           # no colours in the file: the default palette
+    if source.categories_json is not None:                          # (None: a --class-names run without --categories-json)
+        with open(source.categories_json) as f:
+            if not all("color" in c for c in json.load(f)["categories"]):
+                source.categories_json = None                       # no colours in the file: the default palette
     if "panoptic_seg" in output:
         pan, infos = output["panoptic_seg"]
         lut, names, rows = _category_table(source, ov.ALPHA_VPS, len(table["ids"]))
@@ -193,7 +232,12 @@ def image_overlay_table(args, output, table):
 def run_images(args, cfg, model):
     """An image run: records, class table, mapper, writers and evaluators around `inference_on_images`."""
     from .inference.results import image_instances_to_coco_json, write_instances_json, write_panoptic_prediction, write_semseg_prediction
-    if args.image_dir is not None:
+    if getattr(args, "vocabulary", None) is not None:               # --class-names: the class table is the installed vocabulary's
+        from .data.image_datasets import class_table
+        vocab = args.vocabulary
+        records = image_records_from_dir(args.image_dir)
+        table = class_table([{"id": i, "name": n, "isthing": int(vocab.things is None or i in vocab.things)} for i, n in enumerate(vocab.names)])
+    elif args.image_dir is not None:
         records = image_records_from_dir(args.image_dir)
         table = load_categories_json(args.pan_gt_json or args.categories_json)
     else:
@@ -304,6 +348,32 @@ def _legend(lut, names, present):
             for k in sorted(present) if lut[k, 3] > 0}
 
 
+def _class_suffix(vocab, score):
+    """": <name>" of the best class of a VIS result's per-class scores under an installed vocabulary; "" without one."""
+    score = torch.as_tensor(score).reshape(-1)
+    if vocab is None or score.numel() != len(vocab):
+        return ""
+    return ": " + vocab.names[int(score.argmax())]
+
+
+def install_class_names(args, model):
+    """--class-names: the vocabulary of the file, made by the model's own language encoder (or --clip-weights'), installed under
+    --dataset-name, and O/inference/vocabulary.json (contiguous id -> name) beside the results."""
+    from . import vocabulary
+    tpe = getattr(model, "text_prompt_encoder", None)
+    enc = getattr(tpe, "lang_encoder", None)
+    if enc is None:
+        if not args.clip_weights:
+            raise SystemExit("--class-names: the config builds no language encoder; give --clip-weights")
+        enc = vocabulary.build_lang_encoder(args.clip_weights, device=args.device)
+    vocab = vocabulary.Vocabulary.from_file(args.class_names, enc)
+    vocabulary.install(model, vocab, name=args.dataset_name, sub_task=args.sub_task or "vis")
+    os.makedirs(os.path.join(args.output_dir, "inference"), exist_ok=True)
+    with open(os.path.join(args.output_dir, "inference", "vocabulary.json"), "w") as f:
+        json.dump({str(c): n for c, n in enumerate(vocab.names)}, f, indent=1)
+    return vocab
+
+
 def _category_table(args, alpha, n_default):
     """(lut, {row: name}, {category id: row}) from --categories-json ({"categories": [{"id", "name", "color"}]}), or without one the
     default palette with row = id + 1."""
@@ -323,6 +393,8 @@ def overlay_tables(args, inputs, outputs):
     results that carry per-frame masks, through `idmap_from_instances`."""
     from .inference import overlay_rule as ov
     video = inputs[0]
+    vocab = getattr(args, "vocabulary", None)                         # --class-names: row c + 1 is name c where no categories file names it
+    vocab_names = {c + 1: n for c, n in enumerate(vocab.names)} if vocab is not None else {}
     if args.vos:
         vos = args.vos_schedule
         pal = video.get("mask_palette")
@@ -331,7 +403,7 @@ def overlay_tables(args, inputs, outputs):
     if isinstance(outputs, dict) and outputs.get("task") == "vss" and "pred_masks" in outputs:
         sem = torch.as_tensor(outputs["pred_masks"])
         lut, names, rows = _category_table(args, ov.ALPHA_VSS, int(sem.max()) + 1 if sem.numel() else 1)
-        return [(0, sem + 1, lut, names)]                             # contiguous class c: row c + 1 (row 0 is "nothing", transparent)
+        return [(0, sem + 1, lut, names or vocab_names)]              # contiguous class c: row c + 1 (row 0 is "nothing", transparent)
     if isinstance(outputs, dict) and outputs.get("task") == "vps" and "pred_masks" in outputs:
         pan = torch.as_tensor(outputs["pred_masks"]).long()
         infos = outputs["segments_infos"]
@@ -340,7 +412,7 @@ def overlay_tables(args, inputs, outputs):
         for info in infos:                                           # a segment is drawn in its category's colour
             row = rows.get(int(info["category_id"]), 0) if rows is not None else int(info["category_id"])
             ids[pan == int(info["id"])] = row
-        return [(0, ids, lut, names)]
+        return [(0, ids, lut, names or (vocab_names if rows is None else {}))]
     if isinstance(outputs, list) and outputs and all(isinstance(c, list) and all(isinstance(r, dict) and "masks" in r for r in c) for c in outputs):
         tables = []
         for clip in outputs:
@@ -350,7 +422,7 @@ def overlay_tables(args, inputs, outputs):
             scores = torch.stack([torch.as_tensor(r["score"]).float().max() for r in clip])
             lut = ov.lut_from_palette(ov.default_palette(len(clip) + 1))
             tables.append((int(clip[0]["frame_id_start"]), ov.idmap_from_instances(masks, scores), lut,
-                           {k + 1: "object %d" % r["obj_id"] for k, r in enumerate(clip)}))
+                           {k + 1: "object %d" % r["obj_id"] + _class_suffix(vocab, r["score"]) for k, r in enumerate(clip)}))
         return tables
     return "the output holds no per-pixel result at the output size"
 
@@ -386,6 +458,8 @@ def main(argv=None):
     ckpt = torch.load(args.weights, map_location="cpu")
     model.load_state_dict(ckpt["model"], strict=True)
     model = model.to(args.device)
+    if getattr(args, "class_names", None) is not None:
+        args.vocabulary = install_class_names(args, model)
     if getattr(args, "image", False):
         run_images(args, cfg, model)
         return 0
@@ -398,6 +472,9 @@ def main(argv=None):
         records = load_video_json(args.json, args.image_root, args.dataset_name)
     else:
         records = video_records_from_dir(args.video_dir)
+        if getattr(args, "vocabulary", None) is not None:           # the frames run as the installed vocabulary's data set
+            for r in records:
+                r["dataset_name"] = args.dataset_name
     mapper = (VOSTestMapper if args.vos else VideoTestMapper).from_config(cfg, resize=args.resize, device=args.device, decode=getattr(args, "decode", "host"))
     os.makedirs(args.output_dir, exist_ok=True)
     evaluator = build_evaluator(args)

@@ -103,6 +103,11 @@ class Switches:
     # prediction head's chain, and the next layer's cross-attention query projection beside that chain: 9 launches per layer instead
     # of 13.  False: the launch sequence without them.  Bit-identical either way
     decoder_seams: bool = True
+    # TextPromptEncoder.get_expression_prompt through the ragged text tower (CLIPLangEncoder.encode_text_ragged: every text cut at its
+    # end-of-text token, the attention per sequence in csrc/text_attn.hip); `max_batch` then bounds tokens (max_batch x 77), not texts.
+    # OFF by default: the same numbers to fp32 rounding, not bit for bit (the GEMMs see other row counts), and the recorded states
+    # were made on the dense tower
+    text_ragged: bool = False
 
 
 SWITCHES = Switches(
@@ -116,7 +121,7 @@ SWITCHES = Switches(
     fused_sampler=_flag("UNIVS_FUSED_SAMPLER", True), small_mlp_norm=_flag("UNIVS_SMALL_MLP_NORM", True),
     fold_fpn_norm=_flag("UNIVS_FOLD_FPN_NORM", True), fold_attn_merge=_flag("UNIVS_FOLD_ATTN_MERGE", False), swin_channels_last=_flag("UNIVS_SWIN_CHANNELS_LAST", True),
     encoder_pair=_flag("UNIVS_ENCODER_PAIR", True), swin_fused_qkv=_flag("UNIVS_SWIN_FUSED_QKV", True),
-    decoder_seams=_flag("UNIVS_DECODER_SEAMS", True))
+    decoder_seams=_flag("UNIVS_DECODER_SEAMS", True), text_ragged=_flag("UNIVS_TEXT_RAGGED", False))
 if SWITCHES.sampler not in ("auto", "reference", "device"):
     raise ValueError(f"UNIVS_SAMPLER={SWITCHES.sampler!r} (expected 'auto', 'reference' or 'device')")
 
