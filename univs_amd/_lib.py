@@ -2,7 +2,7 @@
 include/univs_fused_hip.h, include/univs_pvos_hip.h, include/univs_semantic_hip.h, include/univs_encoder_hip.h,
 include/univs_swin_hip.h, include/univs_frames_hip.h, include/univs_prompts_hip.h, include/univs_png_hip.h,
 include/univs_hota_hip.h, include/univs_pngread_hip.h, include/univs_jpeg_hip.h, include/univs_jpegenc_hip.h, include/univs_idmap_hip.h,
-include/univs_seam_hip.h, include/univs_imagelabels_hip.h and include/univs_text_hip.h).
+include/univs_seam_hip.h, include/univs_imagelabels_hip.h, include/univs_text_hip.h and include/univs_polygons_hip.h).
 
 The header is the one statement of the ABI: `SIGNATURES` (restype / argtypes of every `univs_*` symbol) and `CONFIG_FIELDS` (the
 members of `struct UnivsConfig`) are read from its text when this module loads -- no table is kept by hand.
@@ -148,6 +148,11 @@ with open(IMAGELABELS_HEADER_PATH) as _f:
 TEXT_HEADER_PATH = os.path.join(_HERE, "..", "include", "univs_text_hip.h")
 with open(TEXT_HEADER_PATH) as _f:
     TEXT_BINDING = parse_signatures(_f.read())
+# The nineteenth header (include/univs_polygons_hip.h: polygon segmentations to run-length boundaries, one workgroup per object), likewise
+# (POLYGONS_BINDING, for the same reason).
+POLYGONS_HEADER_PATH = os.path.join(_HERE, "..", "include", "univs_polygons_hip.h")
+with open(POLYGONS_HEADER_PATH) as _f:
+    POLYGONS_BINDING = parse_signatures(_f.read())
 
 _lib = None
 
@@ -171,7 +176,7 @@ def load():
                               *PVOS_SIGNATURES.items(), *SEMANTIC_SIGNATURES.items(), *ENCODER_SIGNATURES.items(), *SWIN_SIGNATURES.items(),
                               *FRAMES_SIGNATURES.items(), *PROMPTS_SIGNATURES.items(), *PNG_SIGNATURES.items(), *HOTA_SIGNATURES.items(),
                               *PNGREAD_SIGNATURES.items(), *JPEG_SIGNATURES.items(), *JPEGENC_SIGNATURES.items(), *IDMAP_SIGNATURES.items(),
-                              *SEAM_SIGNATURES.items(), *IMAGELABELS_BINDING.items(), *TEXT_BINDING.items()):
+                              *SEAM_SIGNATURES.items(), *IMAGELABELS_BINDING.items(), *TEXT_BINDING.items(), *POLYGONS_BINDING.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing -> loud
         fn.restype = res
         fn.argtypes = args

@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libunivs_hip.so")
-SOURCES = ["capi.hip", "msda_fwd.hip", "msda_tiled2.hip", "msda_strips.hip", "msda_heads.hip", "msda_bwd.hip", "msda_prepare.hip", "mask_decode.hip", "linear_split.hip", "linear_f16x3.hip", "linear_pair_f16x3.hip", "linear_pair_xres.hip", "gemm_f16x3_stream.hip", "conv3x3_wide.hip", "gemm_f16x3_tile.hip", "mlp_f16x3.hip", "small_linear.hip", "cross_attn.hip", "window_attn.hip", "window_attn_f16.hip", "window_attn_qkv.hip", "resample.hip", "semantic_extract.hip", "layer_norm.hip", "group_norm.hip", "softmax.hip", "proca_attn.hip", "prompt_sampler.hip", "transpose.hip", "mask_stats.hip", "image_post.hip", "video_post.hip", "pair_count.hip", "vss_count.hip", "davis_count.hip", "vis_overlap.hip", "pvos_count.hip", "semantic_decode.hip", "frame_resize.hip", "mask_prompt_resize.hip", "png_deflate.hip", "hota_count.hip", "png_inflate.hip", "jpeg_decode.hip", "jpeg_encode.hip", "idmap_prompts.hip", "semseg_labels.hip", "text_attn.hip"]
+SOURCES = ["capi.hip", "msda_fwd.hip", "msda_tiled2.hip", "msda_strips.hip", "msda_heads.hip", "msda_bwd.hip", "msda_prepare.hip", "mask_decode.hip", "linear_split.hip", "linear_f16x3.hip", "linear_pair_f16x3.hip", "linear_pair_xres.hip", "gemm_f16x3_stream.hip", "conv3x3_wide.hip", "gemm_f16x3_tile.hip", "mlp_f16x3.hip", "small_linear.hip", "cross_attn.hip", "window_attn.hip", "window_attn_f16.hip", "window_attn_qkv.hip", "resample.hip", "semantic_extract.hip", "layer_norm.hip", "group_norm.hip", "softmax.hip", "proca_attn.hip", "prompt_sampler.hip", "transpose.hip", "mask_stats.hip", "image_post.hip", "video_post.hip", "pair_count.hip", "vss_count.hip", "davis_count.hip", "vis_overlap.hip", "pvos_count.hip", "semantic_decode.hip", "frame_resize.hip", "mask_prompt_resize.hip", "png_deflate.hip", "hota_count.hip", "png_inflate.hip", "jpeg_decode.hip", "jpeg_encode.hip", "idmap_prompts.hip", "semseg_labels.hip", "text_attn.hip", "polygon_runs.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "msda_common.h"), os.path.join(CSRC, "msda_geometry.h"), os.path.join(CSRC, "msda_dev.h"), os.path.join(CSRC, "msda_window_geom.h"), os.path.join(CSRC, "msda_strips_geom.h"), os.path.join(CSRC, "msda_heads_geom.h"), os.path.join(CSRC, "config.h"), os.path.join(CSRC, "window_attn.h"), os.path.join(CSRC, "f16x3.h"), os.path.join(CSRC, "f16x3_kstep.h"), os.path.join(CSRC, "f16x3_wstream.h"), os.path.join(CSRC, "gemm_plan.h"), os.path.join(CSRC, "pair_xres_plan.h"), os.path.join(CSRC, "conv3x3_wide_plan.h"), os.path.join(CSRC, "resample_taps.h"),
            os.path.join(CSRC, "mask_post.h"), os.path.join(CSRC, "count_core.h"), os.path.join(CSRC, "launchers.h"), os.path.join(CSRC, "xattn_merge.h"), os.path.join(CSRC, "skinny_gemm_f32.h"), os.path.join(CSRC, "png_inflate_core.h"), os.path.join(CSRC, "jpeg_entropy_core.h"), os.path.join(HERE, "..", "include", "univs_hip.h"),
            os.path.join(HERE, "..", "include", "univs_eval_hip.h"), os.path.join(HERE, "..", "include", "univs_fused_hip.h"),
@@ -22,8 +22,11 @@ HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "msda_common.h"), 
            os.path.join(HERE, "..", "include", "univs_pngread_hip.h"), os.path.join(HERE, "..", "include", "univs_jpeg_hip.h"),
            os.path.join(HERE, "..", "include", "univs_jpegenc_hip.h"), os.path.join(CSRC, "jpeg_huff_std.h"),
            os.path.join(HERE, "..", "include", "univs_idmap_hip.h"), os.path.join(HERE, "..", "include", "univs_seam_hip.h"),
-           os.path.join(HERE, "..", "include", "univs_imagelabels_hip.h"), os.path.join(HERE, "..", "include", "univs_text_hip.h")]
+           os.path.join(HERE, "..", "include", "univs_imagelabels_hip.h"), os.path.join(HERE, "..", "include", "univs_text_hip.h"),
+           os.path.join(CSRC, "polygon_core.h"), os.path.join(HERE, "..", "include", "univs_polygons_hip.h")]
 # hota_count.hip promises IEEE operations in the order written (its sums are compared bit for bit with numpy's): no contraction to fma
+# (polygon_runs.hip promises the same and says so in its text: `#pragma clang fp contract(off)` at the head of polygon_core.h, which the
+# host tool compiles too)
 SOURCE_FLAGS = {"hota_count.hip": ["-ffp-contract=off"]}
 
 

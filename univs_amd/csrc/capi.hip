@@ -15,6 +15,7 @@
 #include "../../include/univs_jpeg_hip.h"
 #include "../../include/univs_jpegenc_hip.h"
 #include "../../include/univs_png_hip.h"
+#include "../../include/univs_polygons_hip.h"
 #include "../../include/univs_pngread_hip.h"
 #include "../../include/univs_prompts_hip.h"
 #include "../../include/univs_pvos_hip.h"
@@ -1022,6 +1023,20 @@ int univs_text_attention_f32(const float* qkv, const int* start, int S, long lon
   if (!qkv || !start || !out) return e.null_pointer();
   return e.covered(text_attention_f32(qkv, start, S, Ntok, E, heads, Lmax, scale, out, e.st),
                    "not covered (E / heads in {16, 32, 64}, Lmax <= 128, Ntok 3 E < 2^31, S heads < 2^31)");
+}
+
+// (include/univs_polygons_hip.h)
+int univs_polygons_to_runs(const double* xy, const int* poly_start, const int* obj_start, const int* size, const long long* slot,
+                           long long n_points, int P, int N, long long cap_total, int* bounds, int* ones, int* count, int* status,
+                           void* stream) {
+  const Entry e("univs_polygons_to_runs", stream);
+  if (N < 0 || P < 0 || n_points < 0 || cap_total < 0)
+    return e.invalid("bad arguments n_points=%lld P=%d N=%d cap_total=%lld", n_points, P, N, cap_total);
+  if (N == 0) return UNIVS_OK;
+  if (!xy || !poly_start || !obj_start || !size || !slot || !bounds || !ones || !count || !status) return e.null_pointer();
+  if (n_points >= (1LL << 31) || cap_total >= (1LL << 31))
+    return e.covered(UNIVS_ERR_NOT_IMPLEMENTED, "not covered (n_points < 2^31, cap_total < 2^31)");
+  return polygons_to_runs(xy, poly_start, obj_start, size, slot, n_points, P, N, cap_total, bounds, ones, count, status, e.st);
 }
 
 // (include/univs_seam_hip.h)

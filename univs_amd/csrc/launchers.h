@@ -258,6 +258,10 @@ int label_confusion_u8(const unsigned char* gt, const unsigned char* pred, long 
 int text_attention_f32(const float* qkv, const int* start, int S, long long Ntok, int E, int heads, int Lmax, float scale, float* out,
                        hipStream_t st);
 
+// ---- polygon_runs.hip: returns UNIVS_OK or the launch's error (the entry answers what is not covered)
+int polygons_to_runs(const double* xy, const int* poly_start, const int* obj_start, const int* size, const long long* slot, long long n_points,
+                     int P, int N, long long cap_total, int* bounds, int* ones, int* count, int* status, hipStream_t st);
+
 // ---- png_deflate.hip: returns UNIVS_OK, UNIVS_ERR_NOT_IMPLEMENTED where the sizes are not covered, or the launch's error
 int png_deflate_maps(const void* src, int src_is_i32, int N, int H, int W, const unsigned char* lut, int K, int C, int rows_per_stripe,
                      unsigned char* scratch, unsigned char* out, long long* offsets, hipStream_t st);

@@ -16,7 +16,7 @@ explicit arguments in place of detectron2's MetadataCatalog and the counts made 
                       `evaluate` is detectron2's rule (`semseg_scores`), restated from its documented behaviour, unpinned.
   evaluate_panoptic_files / evaluate_semseg_files, and `python -m univs_amd.evaluation.image`: files already on disk.
 
-Mask AP is not scored: COCO's instance ground truth is polygons and no polygon rasteriser is built here.  Single process.
+Mask AP is scored by evaluation/coco.py (COCO's instance ground truth is polygons: polygon_ops.py).  Single process.
 """
 import argparse
 import json

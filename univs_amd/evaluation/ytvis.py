@@ -98,6 +98,8 @@ class YTVISEval:
     [] where there is neither}, `eval` {'precision' [T, R, K, A, M], 'recall' [T, K, A, M], 'scores'}, `stats` [12], `summary` (the
     twelve lines the reference prints)."""
 
+    area_rng = AREA_RNG                      # (evaluation/coco.py: COCOSegmEval shares everything below _video_ious and has COCO's ranges)
+
     def __init__(self, dataset, results, device=None):
         self.dataset, self.device = dataset, _device(device)
         self.videos = {v["id"]: v for v in dataset["videos"]}
@@ -167,7 +169,7 @@ class YTVISEval:
                     rows = [self._dt_row[id(dt[i])] for i in order]
                     cols = [self._gt_col[id(g)] for g in gt]
                     self.ious[vid, cat] = table[np.ix_(rows, cols)].reshape(len(rows), len(cols))
-        self.eval_vids = [self._evaluate_vid(vid, cat, rng, top) for cat in self.cat_ids for rng in AREA_RNG for vid in self.vid_ids]
+        self.eval_vids = [self._evaluate_vid(vid, cat, rng, top) for cat in self.cat_ids for rng in self.area_rng for vid in self.vid_ids]
 
     # ---- evaluateVid ---------------------------------------------------------------------------------------------------------------------
     def _evaluate_vid(self, vid, cat, rng, max_det):
@@ -212,7 +214,7 @@ class YTVISEval:
 
     # ---- accumulate ----------------------------------------------------------------------------------------------------------------------
     def accumulate(self):
-        n_thr, R, K, A, M = len(IOU_THRS), len(REC_THRS), len(self.cat_ids), len(AREA_RNG), len(MAX_DETS)
+        n_thr, R, K, A, M = len(IOU_THRS), len(REC_THRS), len(self.cat_ids), len(self.area_rng), len(MAX_DETS)
         I = len(self.vid_ids)
         precision = -np.ones((n_thr, R, K, A, M))
         recall = -np.ones((n_thr, K, A, M))

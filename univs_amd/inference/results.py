@@ -648,7 +648,8 @@ def image_instances_to_coco_json(inputs: dict, output: dict, contiguous_id_to_da
 
 
 def write_instances_json(records: Sequence[dict], output_dir: str) -> str:
-    """The records of every image -> `<output_dir>/inference/coco_instances_results.json`.  Mask AP is not scored here."""
+    """The records of every image -> `<output_dir>/inference/coco_instances_results.json`, which
+    evaluation/coco.py scores (mask AP)."""
     import json
     save_dir = os.path.join(output_dir, "inference")
     os.makedirs(save_dir, exist_ok=True)

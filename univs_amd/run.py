@@ -6,7 +6,7 @@
                             [--visualize off|host|gpu [--categories-json C]]
                             [--gt-json G [--hota] | --pan-gt-json P --truth-dir T | --davis-root V | --pvos-data V]
                             [KEY VALUE ...]
-    python -m univs_amd.run --config-file F --weights W (--image-dir D | --pan-gt-json P --image-root R --truth-dir T [--sem-gt-dir S])
+    python -m univs_amd.run --config-file F --weights W (--image-dir D | --pan-gt-json P --image-root R --truth-dir T [--sem-gt-dir S]) [--inst-gt-json G]
                             --dataset-name coco_panoptic|coco|ade20k --output-dir O [--categories-json C] [--batch B] ...
 
 The model is `build_model(load_cfg(F, [KEY VALUE ...]))` with `ckpt["model"]` loaded strictly (the reference's state-dict layout).  The
@@ -47,7 +47,8 @@ from P's own `categories`, without P from --categories-json; the driver's `thing
 is asked for as labels (`sem_seg_as = "labels"`: csrc/semseg_labels.hip).  Written are O/inference/panoptic/<stem>.png with
 O/inference/predictions.json (the segments' classes), O/inference/sem_seg/<stem>.png and O/inference/coco_instances_results.json, for the sub-tasks the config enables.  With P and T the
 panoptic results are scored by evaluation.image.PanopticEvaluator (PQ / SQ / RQ), with --sem-gt-dir S (class-id PNGs named after the
-images) the semantic ones by SemSegEvaluator (mIoU); both dictionaries are printed as one.  Mask AP is not scored.  --visualize draws
+images) the semantic ones by SemSegEvaluator (mIoU); both dictionaries are printed as one.  With --inst-gt-json G (a COCO
+instances json, polygons) the instance results are scored with evaluation.coco.COCOInstanceEvaluator: mask AP.  --visualize draws
 the panoptic map, else the semantic labels, to O/inference/Overlays.
 
 A vocabulary of one's own: --class-names F (a text file, one name per line, or a json with a `categories` list) with --video-dir or
@@ -88,6 +89,8 @@ def parse_args(argv=None):
     ap.add_argument("--vos-meta", help="with --masks-dir: the folder of meta.json / obj_class.json (default: the one above --masks-dir)")
     ap.add_argument("--image-dir", help="a folder of jpg / png images: the per-image driver (with --dataset-name coco_panoptic, coco or ade20k)")
     ap.add_argument("--sem-gt-dir", help="an image run: the folder of class-id PNGs named after the images, scored with SemSegEvaluator")
+    ap.add_argument("--inst-gt-json", default=argparse.SUPPRESS,      # (absent from the namespace unless given: the other runs' namespaces stay theirs)
+                    help="an image run: a COCO instances json (polygons), the instance results scored with COCOInstanceEvaluator")
     ap.add_argument("--batch", type=int, default=1, help="an image run: images per model call")
     ap.add_argument("--output-dir", required=True)
     ap.add_argument("--resize", choices=("gpu", "host"), default="gpu")
@@ -119,6 +122,8 @@ def parse_args(argv=None):
                                                 args.pan_gt_json is not None and args.image_root is not None)
     if args.image:
         return check_image_args(ap, args)
+    if hasattr(args, "inst_gt_json"):
+        ap.error("--inst-gt-json goes with an image run (--image-dir, or --pan-gt-json with --image-root and an image --dataset-name)")
     if args.sem_gt_dir is not None or args.batch != 1:
         ap.error("--sem-gt-dir and --batch go with an image run (--image-dir, or --pan-gt-json with --image-root and an image --dataset-name)")
     if from_json == (args.video_dir is not None):
@@ -157,7 +162,7 @@ def check_class_name_args(ap, args):
         ap.error("--class-names goes with --video-dir or --image-dir, not with --json (a registered data set has its named vocabulary)")
     if args.masks_dir is not None:
         ap.error("--class-names is not for a VOS run (--masks-dir): it has no class vocabulary")
-    if args.gt_json or args.pan_gt_json or args.sem_gt_dir or args.davis_root or args.pvos_data:
+    if args.gt_json or args.pan_gt_json or args.sem_gt_dir or hasattr(args, "inst_gt_json") or args.davis_root or args.pvos_data:
         ap.error("--class-names: the ground truth of a registered data set does not share a vocabulary made from names; no evaluator")
     if args.image_dir is not None and args.sub_task is not None:
         ap.error("--sub-task chooses what the video entity loop produces; an image run has none")
@@ -185,6 +190,8 @@ def check_image_args(ap, args):
         ap.error("--masks-dir, --vos-meta, --gt-json, --hota, --davis-root and --pvos-data belong to video runs")
     if args.batch < 1:
         ap.error("--batch is at least 1")
+    if hasattr(args, "inst_gt_json") and not os.path.isfile(args.inst_gt_json):
+        ap.error(f"--inst-gt-json: {args.inst_gt_json} is not a file")
     args.vos = False
     return args
 
@@ -269,11 +276,30 @@ def run_images(args, cfg, model):
     results = inference_on_images(model, records, mapper, evaluators, on_output=on_output, batch=args.batch)
     if driver.instance_on:
         write_instances_json(instances, args.output_dir)
+    if getattr(args, "inst_gt_json", None):
+        results = score_instances(args, instances, results)
     if panoptic:                                                     # (the segments' classes: what PanopticEvaluator.evaluate writes when it runs)
         with open(os.path.join(args.output_dir, "inference", "predictions.json"), "w") as f:
             json.dump({"annotations": panoptic}, f)
-    if evaluators:
+    if evaluators or getattr(args, "inst_gt_json", None):
         print(json.dumps(results, default=str))
+    return results
+
+
+def score_instances(args, instances, results):
+    """--inst-gt-json: mask AP of the instance records the run just wrote; the twelve summary lines are printed, the numbers join
+    `results` under "segm"."""
+    from .evaluation.coco import COCOInstanceEvaluator
+    if not instances:
+        print("--inst-gt-json: the run produced no instance records (the driver's instance output is off, or nothing was found); no mask AP")
+        return results
+    ev = COCOInstanceEvaluator(args.inst_gt_json, os.path.join(args.output_dir, "inference"), device=args.device)
+    ev.process(instances)
+    scores = ev.evaluate()
+    for line in ev.last_eval.summary:
+        print(line)
+    results = dict(results) if results else {}
+    results.update(scores)
     return results
 
 
